@@ -5,7 +5,7 @@ Own counterpart of /root/reference/bench_moe.py:110-132 (same operator, same arg
 weight/input clones), with the dims swapped to Qwen3-30B-A3B (K=2048, N=768, E=128, top-8:
 /root/reference/models/Qwen3-VL-30B-A3B-Instruct/config.json:16,22,25,26), HIP-event timing and warm-up.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tokens M_per_gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tokens M_per_gpu] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N ...
 
@@ -14,7 +14,12 @@ One "step" = one fused_experts call over one batch of synthetic tokens already r
   N > 1 : expert parallel (weak scaling: every rank brings its own `--tokens` tokens and owns E/N experts);
           dispatch / combine by RCCL all-to-all (sgl_kernel/expert_parallel.py).
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel = GEMM-1, timed by
-HIP events on its own stream inside the timed region) and, at N = 1, `cpu_baseline` (plain-C oracle on the host).
+HIP events on its own stream inside the timed region).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds, at N = 1, everything that takes runs
+of its own: the oracle check of the timed call (`verified`), the secondary `a8` and `int8` measurements and `cpu_baseline`
+(plain-C oracle on the host); `--no-verify`, `--no-a8`, `--no-int8` and `--no-cpu-baseline` take single ones out again.
+`--dump-outputs DIR` writes the output of the last timed step to DIR/out.npy (float32; see dump_outputs).
 """
 import argparse
 import ctypes
@@ -108,6 +113,23 @@ def cpu_baseline(a, w1, w2, w1s, w2s, tw, ids, max_tokens):
                       f"sgl_kernel)"}
 
 
+DUMP_MAX_BYTES = 32 << 20
+
+
+def dump_outputs(out, directory):
+    """Writes what the last timed step returned, [M, K] bf16, as `directory`/out.npy in float32.  An output above 32 MiB
+    (M > 4096 at K = 2048) is cut down to a sample of its rows, drawn once from a fixed seed and kept in ascending order, so
+    that two runs with the same arguments write the same rows."""
+    import numpy as np
+    M = int(out.shape[0])
+    n = min(M, DUMP_MAX_BYTES // (int(out.shape[1]) * 4))
+    if n < M:
+        rows = torch.randperm(M, generator=torch.Generator().manual_seed(20240229))[:n].sort().values
+        out = out[rows.to(out.device)]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "out.npy"), out.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -117,6 +139,11 @@ def main():
                     help="tokens per GPU per step (BASELINE.md evaluates the MFMA roofline at M = 16384)")
     ap.add_argument("--cpu-tokens", type=int, default=int(os.environ.get("SGLK_BENCH_CPU_TOKENS", 16384)),
                     help="cpu_baseline: at most this many tokens of the GPU run's batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/out.npy (float32, at most 32 MiB: a fixed sample of rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (N = 1): the oracle check of the timed call, the "
+                         "secondary a8 and int8 measurements, cpu_baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-a8", dest="a8", action="store_false",
                     help="skip the secondary measurement of the opt-in a8 mode (fp8 activations, block-scaled fp8 MFMA)")
@@ -126,6 +153,8 @@ def main():
     ap.add_argument("--out-of-place", dest="inplace", action="store_false",
                     help="inplace=False (the default is the reference's inplace=True, bench_moe.py:113-130)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -155,9 +184,11 @@ def main():
     LCLONES = 2   # rotate over clones like bench_moe.py:50-58; 2 x 604 MB at N=1 exceeds the 256 MiB Infinity Cache
     a, w1, w2, w1s, w2s, tw, ids = make_inputs(M, E_local, dev, 1111 + rank)
     w1p, w2p = ops.convert_weight_packed(w1), ops.convert_weight_packed(w2)
-    verify = world == 1 and not args.no_verify
+    extras = args.full and world == 1     # what only --full runs
+    verify = extras and not args.no_verify
+    want_cpu = extras and not args.no_cpu_baseline
     # the oracle check after the timed region and the cpu_baseline read the plain (unpacked) weights
-    w_host = (w1.cpu(), w2.cpu()) if (verify or (world == 1 and not args.no_cpu_baseline)) else None
+    w_host = (w1.cpu(), w2.cpu()) if (verify or want_cpu) else None
     del w1, w2
     # inplace=True is the reference's call (bench_moe.py:113-130): every step overwrites its input.  So that no step ever
     # reads a previous step's OUTPUT (values would drift towards 0 / inf and the chip clocks differently on such data), each
@@ -165,6 +196,9 @@ def main():
     prime = max(0, 12 - args.warmup)
     n_inputs = min(96, prime + args.warmup + args.steps) if (args.inplace and world == 1) else LCLONES
     inputs = [a.clone() for _ in range(n_inputs)]
+    # --dump-outputs: beyond 96 steps the clones are reused, and a reused clone holds an earlier step's output.  So that the
+    # step whose output is written reads the pristine tokens whatever --steps is, the last timed step gets a clone of its own.
+    last_input = a.clone() if (args.dump_outputs and args.inplace and world == 1) else None
     w1ps = [w1p.clone() for _ in range(LCLONES)]
     w2ps = [w2p.clone() for _ in range(LCLONES)]
     del w1p, w2p
@@ -212,6 +246,7 @@ def main():
         def step():
             out = ep(inputs[step_idx[0] % n_inputs], tw, ids)
             step_idx[0] += 1
+            last["out"] = out
             return out
 
     def barrier():
@@ -251,11 +286,18 @@ def main():
     _ops.set_stage_timer(timer)
     L.sglk_stage_timer_reset(timer)
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    if last_input is None:
+        run_steps(args.steps)
+    else:
+        run_steps(args.steps - 1)
+        inputs[step_idx[0] % n_inputs] = last_input     # a list entry on the host: no GPU work
+        run_steps(1)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
     _ops.set_stage_timer(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last["out"], args.dump_outputs)
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
@@ -482,17 +524,17 @@ def main():
                           "exact counts, one host read per step", "overflow_mask": ovf, **ep.last_stats}
             if ovf:
                 line["verified"] = False       # a segment overflowed: tokens were dropped, the number is not valid
-        if world == 1 and args.a8:
+        if extras and args.a8:
             try:
                 line["a8"] = bench_a8()
             except Exception as e:
                 line["a8"] = {"value": None, "error": str(e)[:300]}
-        if world == 1 and args.int8:
+        if extras and args.int8:
             try:
                 line["int8"] = bench_int8()
             except Exception as e:
                 line["int8"] = {"value": None, "error": str(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             try:
                 line["cpu_baseline"] = cpu_baseline(a, w_host[0], w_host[1], w1s, w2s, tw, ids, args.cpu_tokens)
             except Exception as e:  # the bench line must still be printed

@@ -9,7 +9,7 @@ i=0
 while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
-  rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OUT/pass$i" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify "$@" > "$OUT/pass$i.log" 2>&1 || echo "pass $i failed"
+  rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OUT/pass$i" -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-verify "$@" > "$OUT/pass$i.log" 2>&1 || echo "pass $i failed"
 done <<GROUPS
 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE
