@@ -397,6 +397,15 @@ int sglk_qkv_proj_with_rope(const sglk_qkv_proj_args* args, void* stream);
  * --------------------------------------------------------------------------------------------------------- */
 int sglk_bmm_heads(const void* x, int64_t x_stride_b, int64_t x_stride_h, const void* w, int32_t packed, void* out,
                    int64_t out_stride_b, int64_t out_stride_h, int32_t B, int32_t H, int32_t OC, int32_t IC, void* stream);
+/* bmm_heads with fp8 (e4m3fn) weights and one per-tensor scale (bmm_cpu's `scale` argument: w_kc / w_vc of fp8 MLA checkpoints):
+ *   out[b][h][oc] = bf16( *scale * sum_ic x[b][h][ic] * float(w[h][oc][ic]) )      torch.bmm(A, B.to(bf16)) * s, test_bmm_fp8.py
+ * x / out bf16 with strides in elements (contiguous last dim), fp32 accumulation on the bf16 matrix pipe after an exact
+ * fp8 -> bf16 conversion, the scale applied in fp32, one rounding.  w [H][OC][IC] row-major (8-byte aligned) or, with packed != 0,
+ * per head in convert_weight_packed's fp8 order (OC % 16 == 0, IC % 64 == 0, 16-byte aligned); both give identical bits.
+ * IC % 8 == 0.  scale is a DEVICE pointer to one float, read by the kernel: no host synchronisation, graph-capturable. */
+int sglk_bmm_heads_fp8(const void* x, int64_t x_stride_b, int64_t x_stride_h, const void* w, int32_t packed, const float* scale,
+                       void* out, int64_t out_stride_b, int64_t out_stride_h, int32_t B, int32_t H, int32_t OC, int32_t IC,
+                       void* stream);
 int sglk_rope_gptj(const void* q_pe, int64_t q_stride_b, int64_t q_stride_h, const void* k_pe, int64_t k_stride_b,
                    const void* positions, int32_t positions_is64, const void* cos_sin_cache, int64_t cache_stride,
                    void* q_out, int64_t q_out_stride_b, int64_t q_out_stride_h, void* k_out, int64_t k_out_stride_b,

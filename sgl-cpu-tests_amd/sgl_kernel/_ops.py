@@ -933,15 +933,22 @@ _impl("mxfp4_scaled_mm_cpu", mxfp4_scaled_mm_cpu)
 
 
 # bmm_cpu: /root/reference/test_bmm_fp8.py:38-39,67,73 -- out[b] = mat1[b] @ mat2[b]^T, bf16, strided out / mat1 views
+# mat2 bf16 (vector kernel, scale=None) or float8_e4m3fn with its per-tensor scale (matrix-core kernel, csrc/bmm_fp8.hip)
 _DEF.define("bmm_cpu(Tensor(a!) out, Tensor mat1, Tensor mat2, bool is_vnni, Tensor? scale) -> ()")
 
 
 def bmm_cpu(out, mat1, mat2, is_vnni, scale):
-    if scale is not None:
-        raise RuntimeError("bmm_cpu: scaled (fp8) mat2 is not supported; the reference harness passes scale=None")
+    fp8 = mat2.dtype == torch.float8_e4m3fn
+    if fp8:
+        if scale is None:
+            raise RuntimeError("bmm_cpu: a float8_e4m3fn mat2 needs its per-tensor scale")
+        if scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != mat2.device:
+            raise RuntimeError("bmm_cpu: scale must be a float32 tensor of one element on mat2's device")
+    elif scale is not None:
+        raise RuntimeError("bmm_cpu: a scale goes with a float8_e4m3fn mat2 only")
     for t, n in ((out, "out"), (mat1, "mat1"), (mat2, "mat2")):
-        if t.dim() != 3 or t.dtype != torch.bfloat16:
-            raise RuntimeError(f"bmm_cpu: {n} must be a 3-D bfloat16 tensor")
+        if t.dim() != 3 or (t.dtype != torch.bfloat16 and not (fp8 and t is mat2)):
+            raise RuntimeError(f"bmm_cpu: {n} must be a 3-D bfloat16 tensor" + (" (mat2: or float8_e4m3fn)" if t is mat2 else ""))
     Bn, M, K = mat1.shape
     N = mat2.shape[1]
     if mat2.shape[0] != Bn or mat2.shape[2] != K or tuple(out.shape) != (Bn, M, N):
@@ -951,6 +958,11 @@ def bmm_cpu(out, mat1, mat2, is_vnni, scale):
         raise RuntimeError("bmm_cpu: out / mat1 need a contiguous last dim, mat2 must be contiguous [B, N, K]")
     # kernel naming: "heads" = the bmm batch, "rows" = M (sglk.h: out[b][h][oc] = sum_ic x[b][h][ic] * w[h][oc][ic])
     packed = 1 if (is_vnni and _pack_supported(N, K, mat2.dtype)) else 0
+    if fp8:
+        # the kernel reads the scale from device memory: no host synchronisation, the call can be captured in a graph
+        _lib.check(_lib.lib().sglk_bmm_heads_fp8(_ptr(mat1), mat1.stride(1), mat1.stride(0), _ptr(mat2), packed, _ptr(scale),
+                                                 _ptr(out), out.stride(1), out.stride(0), M, Bn, N, K, _stream(out)), "bmm_cpu")
+        return
     _lib.check(_lib.lib().sglk_bmm_heads(_ptr(mat1), mat1.stride(1), mat1.stride(0), _ptr(mat2), packed, _ptr(out),
                                          out.stride(1), out.stride(0), M, Bn, N, K, _stream(out)), "bmm_cpu")
 

@@ -2,7 +2,7 @@
 """Secondary measurements (not the driver's bench.py): the M sweep of fp8 fused_experts and the other
 operators of SURVEY.md §8 at the shapes the reference benches, each against the roofline that bounds it.
 
-    python tools/bench_ops.py [moe|moe_literal|moe_int8|gemm|attn|absorb|rows|all] > gpurun_out/bench_ops.json
+    python tools/bench_ops.py [moe|moe_literal|moe_int8|gemm|mxfp4|bmm|attn|absorb|rows|all] > bench_ops.json
 
 Prints one JSON object per line.  HIP-event timing on the current stream, warm-up, rotating clones where the working
 set would otherwise sit in the 256 MiB Infinity Cache.
@@ -310,8 +310,7 @@ def bench_block():
 def bench_mxfp4():
     """mxfp4_scaled_mm_cpu (/root/reference/test_mxfp4.py): W4A16.  Small M: weights expanded to bf16 in the generic engine's
     loader, bound by the weight bytes (N*K/2 + scales); large M: the fp4 weights as stored on the block-scaled matrix cores
-    (gemm_mxfp4.hip), priced against the bf16 roof (two e4m3 terms per activation = the bf16 rate); bmm_cpu rides along
-    (test_bmm_fp8.py:131-132)."""
+    (gemm_mxfp4.hip), priced against the bf16 roof (two e4m3 terms per activation = the bf16 rate)."""
     g = torch.Generator(device="cuda").manual_seed(4)
     for (M, N, K) in ((1, 4096, 4096), (16, 4096, 4096), (128, 4096, 4096), (1024, 12288, 2048), (4096, 4096, 4096)):
         x = (torch.randn(M, K, device="cuda", generator=g) / 10).bfloat16()
@@ -323,12 +322,36 @@ def bench_mxfp4():
         t_hbm, t_mfma = byts / (PEAK_HBM * 1e9), flop / (PEAK_BF16 * 1e12)
         emit(op="mxfp4_scaled_mm", M=M, N=N, K=K, ms=round(ms, 4), tflops=round(flop / ms / 1e9, 2), gbps=round(byts / ms / 1e6, 1),
              bound="hbm" if t_hbm > t_mfma else "mfma", roofline_frac=round(max(t_hbm, t_mfma) * 1e3 / ms, 4))
-    for (B, M, N, K) in ((16, 1, 512, 128), (16, 1, 128, 512), (16, 64, 512, 128)):
+
+
+def bench_bmm():
+    """bmm_cpu (the reference's test_bmm_fp8.py:131-132) on the MLA w_kc / w_vc shapes, packed weights, strided views: the bf16
+    vector kernel and the fp8 (e4m3 + tensor scale) matrix-core kernel at the same shapes.  `ms` is the eager call (host enqueue
+    included); `ms_device` the median of three hipGraph replays taken alternately for the two (`ms_device_runs` shows the spread);
+    the fp8 row's rates are the shapes' bytes and FLOPs over `ms_device`."""
+    g = torch.Generator(device="cuda").manual_seed(4)
+    for (B, M, N, K) in ((16, 1, 512, 128), (16, 1, 128, 512), (16, 64, 512, 128), (16, 256, 512, 128), (128, 128, 512, 128)):
         a = torch.randn(M, B, K + 64, device="cuda", generator=g).bfloat16().narrow(2, 0, K).transpose(0, 1)
-        w = ops.convert_weight_packed(torch.randn(B, N, K, device="cuda", generator=g).bfloat16())
+        wf = torch.randn(B, N, K, device="cuda", generator=g)
+        w = ops.convert_weight_packed(wf.bfloat16())
+        w8 = ops.convert_weight_packed((wf * 100).clamp(-448, 448).to(torch.float8_e4m3fn))
+        sc = torch.tensor(0.01, device="cuda")
         out = torch.empty(M, B, N + 64, device="cuda", dtype=torch.bfloat16).narrow(2, 0, N).transpose(0, 1)
-        ms = timed(lambda i: ops.bmm_cpu(out, a, w, True, None), 20)
-        emit(op="bmm_cpu", B=B, M=M, N=N, K=K, ms=round(ms, 4), gbps=round(2 * B * N * K / ms / 1e6, 1), bound="launch")
+        calls = {"bmm_cpu": lambda: ops.bmm_cpu(out, a, w, True, None), "bmm_cpu_fp8": lambda: ops.bmm_cpu(out, a, w8, True, sc)}
+        ms = {k: timed(lambda i: f(), 20) for k, f in calls.items()}
+        runs = {k: [] for k in calls}
+        for _ in range(3):
+            for k, f in calls.items():
+                runs[k].append(graph_ms(f))
+        dev = {k: sorted(v)[1] for k, v in runs.items()}
+        emit(op="bmm_cpu", B=B, M=M, N=N, K=K, ms=round(ms["bmm_cpu"], 4), gbps=round(2 * B * N * K / ms["bmm_cpu"] / 1e6, 1),
+             bound="launch", ms_device=round(dev["bmm_cpu"], 5), ms_device_runs=[round(v, 5) for v in runs["bmm_cpu"]])
+        byts, flop = B * N * K + 2 * B * M * (N + K), 2 * B * M * N * K
+        t_hbm, t_mfma = byts / (PEAK_HBM * 1e9), flop / (PEAK_BF16 * 1e12)
+        emit(op="bmm_cpu_fp8", B=B, M=M, N=N, K=K, ms=round(ms["bmm_cpu_fp8"], 4), ms_device=round(dev["bmm_cpu_fp8"], 5),
+             ms_device_runs=[round(v, 5) for v in runs["bmm_cpu_fp8"]], gbps=round(byts / dev["bmm_cpu_fp8"] / 1e6, 1),
+             tflops=round(flop / dev["bmm_cpu_fp8"] / 1e9, 3), bound="launch" if M == 1 else ("hbm" if t_hbm > t_mfma else "mfma"),
+             vs_bf16_device=round(dev["bmm_cpu"] / dev["bmm_cpu_fp8"], 3))
 
 
 def bench_attn():
@@ -437,7 +460,7 @@ def bench_rows():
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
-    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "attn": bench_attn, "absorb": bench_absorb, "rows": bench_rows}
+    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "absorb": bench_absorb, "rows": bench_rows}
     for name, fn in table.items():
         if which in ("all", name):
             fn()
