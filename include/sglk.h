@@ -510,6 +510,37 @@ typedef struct {
 int sglk_decode_attention(const sglk_decode_attention_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * decode_attention_fp8kv      torch.ops.sgl_kernel.decode_attention_fp8kv: decode_attention over a float8_e4m3fn KV cache
+ *                             with one scale per tensor (the project's own operator; csrc/attention_fp8kv.hip)
+ * 1. k_buffer[loc[b]] = e4m3(clamp(float(key[b]) / k_scale, -448, 448)), v_buffer likewise with v_scale (fp32 division and
+ *    clamp, round to nearest even); with an aliased cache (v_buffer = k_buffer[..., :DV]) value wins in the first DV columns
+ *    and the two scales must be equal,
+ * 2. o[b, h] = v_scale * softmax_j(cap(sm_scale * k_scale * q[b, h] . float(K[j]))) @ float(V[j]) over the cache as it
+ *    stands after the write; splits, attn_logits and the merge as in decode_attention.
+ * q, key, value, o are bf16 (strides in elements); k_buffer / v_buffer are fp8 bytes: their strides and base pointers
+ * must be multiples of 16.  Head dims 576/512, 128/128, 192/128, 64/64; anything else is SGLK_ERR_SHAPE.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* q;
+    void *k_buffer, *v_buffer, *o;
+    const void *key, *value;
+    int64_t q_stride[2], k_buffer_stride[2], v_buffer_stride[2], o_stride[2], key_stride[2], value_stride[2];
+    const void* loc;                 /* [B] int32 or int64 */
+    int32_t loc_is64;
+    float* attn_logits;
+    const void* req_to_token;        /* [B][L] int32 or int64 */
+    int64_t req_to_token_stride;
+    int32_t req_to_token_is64;
+    const int64_t* b_req_idx;
+    const int64_t* b_seq_len;
+    int32_t B, HQ, HKV, D, DV, splits;
+    float sm_scale, logit_cap;
+    float k_scale, v_scale;
+} sglk_decode_attention_fp8kv_args;
+
+int sglk_decode_attention_fp8kv(const sglk_decode_attention_fp8kv_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Stages of fused_experts exposed for tests and profiling (same kernels the fused call launches).
  * moe_align: counting sort of the M*topk slots by expert (ids outside [0,E) dropped), stable in slot order.
  *   sorted_slot [M*topk] i32   slot = m*topk + j, grouped by expert

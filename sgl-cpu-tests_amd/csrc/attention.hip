@@ -19,6 +19,7 @@
 // k_buffer[..., :DV], /root/reference/test_mla.py:83) the K image is reused for V and K is read from HBM once.
 // fp32 softmax, bf16 P, fp32 accumulation; optional logit soft-cap.  Decode writes per-split (O/l, lse) into the
 // caller's attn_logits [B][HQ][splits][DV+1] and a merge kernel combines them.
+#include "attention_internal.h"
 #include "knobs.h"
 
 namespace sglk {
@@ -1478,6 +1479,35 @@ extern "C" int sglk_flash_attn_varlen(const sglk_flash_attn_varlen_args* a, void
     SGLK_FAIL(SGLK_ERR_SHAPE, "flash_attn_varlen: padded head dims D=%d DV=%d not built", Dp, DVp);
 }
 
+// Splits actually used (<= the caller's scratch depth; the merge reads only these): every (request, kv head, split) is one
+// workgroup and a wide-head (D >= 256) workgroup owns a CU, so more workgroups than CUs run in ROUNDS that each pay the
+// prologue (page lookups, first tile) again.  Use the most splits that still fit one round (SGLK_DEC_SPLITS=n forces n, -1 =
+// all).  Measured (MLA, D = 576): B = 40 x 1064 keys 45.7 -> 32.9 us, B = 128 x 4096 keys 177 -> 134 us (3.4 -> 4.5 TB/s).
+int sglk::attn::decode_effective_splits(int B, int HKV, int D, int splits) {
+    int eff = splits;
+    const int64_t per_split = (int64_t)B * HKV;
+    const int cus = attn_cus();
+    if (knobs().dec_splits > 0) eff = knobs().dec_splits < splits ? knobs().dec_splits : splits;
+    else if (knobs().dec_splits == 0 && D >= 256 && per_split * eff > cus) {   // narrow heads: several workgroups share a CU
+        eff = (int)(cus / per_split);
+        if (eff < 1) eff = 1;
+    } else if (knobs().dec_splits == 0 && D < 256 && per_split * eff > (int64_t)8 * cus) {
+        // narrow heads with many (request, kv head) pairs: beyond ~8 workgroups per CU more splits only add prologues (page
+        // lookups, first tile) -- 40 requests x 22 MHA heads x 8 splits of a 33-key sequence were 7040 workgroups and 52 us
+        eff = (int)((int64_t)8 * cus / per_split);
+        if (eff < 1) eff = 1;
+    }
+    return eff;
+}
+
+int sglk::attn::launch_decode_merge(const float* attn_logits, void* o, int64_t o_s0, int64_t o_s1, int B, int HQ, int eff, int splits,
+                                    int DV, hipStream_t stream) {
+    hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)B, (unsigned)HQ), dim3(256), 0, stream, attn_logits, (unsigned short*)o,
+                       o_s0, o_s1, HQ, eff, splits, DV);
+    SGLK_CHECK_LAUNCH("decode_attention(merge)");
+    return SGLK_OK;
+}
+
 extern "C" int sglk_decode_attention(const sglk_decode_attention_args* a, void* stream) {
     SGLK_REQUIRE(a, SGLK_ERR_INVALID, "decode_attention: null args");
     SGLK_REQUIRE(a->B >= 0 && a->HQ > 0 && a->HKV > 0 && a->HQ % a->HKV == 0, SGLK_ERR_INVALID,
@@ -1519,25 +1549,7 @@ extern "C" int sglk_decode_attention(const sglk_decode_attention_args* a, void* 
     p.vb_s0 = a->v_buffer_stride[0]; p.vb_s1 = a->v_buffer_stride[1]; p.logits = a->attn_logits;
     p.req_to_token = a->req_to_token; p.rtt_stride = a->req_to_token_stride; p.rtt_is64 = a->req_to_token_is64;
     p.b_req_idx = a->b_req_idx; p.b_seq_len = a->b_seq_len; p.HQ = a->HQ; p.HKV = a->HKV;
-    // Splits actually used (<= the caller's scratch depth; the merge reads only these): every (request, kv head, split) is one
-    // workgroup and a wide-head (D >= 256) workgroup owns a CU, so more workgroups than CUs run in ROUNDS that each pay the
-    // prologue (page lookups, first tile) again.  Use the most splits that still fit one round (SGLK_DEC_SPLITS=n forces n, -1 =
-    // all).  Measured (MLA, D = 576): B = 40 x 1064 keys 45.7 -> 32.9 us, B = 128 x 4096 keys 177 -> 134 us (3.4 -> 4.5 TB/s).
-    int eff = a->splits;
-    {
-        const int64_t per_split = (int64_t)a->B * a->HKV;
-        const int cus = attn_cus();
-        if (knobs().dec_splits > 0) eff = knobs().dec_splits < a->splits ? knobs().dec_splits : a->splits;
-        else if (knobs().dec_splits == 0 && a->D >= 256 && per_split * eff > cus) {   // narrow heads: several workgroups share a CU
-            eff = (int)(cus / per_split);
-            if (eff < 1) eff = 1;
-        } else if (knobs().dec_splits == 0 && a->D < 256 && per_split * eff > (int64_t)8 * cus) {
-            // narrow heads with many (request, kv head) pairs: beyond ~8 workgroups per CU more splits only add prologues (page
-            // lookups, first tile) -- 40 requests x 22 MHA heads x 8 splits of a 33-key sequence were 7040 workgroups and 52 us
-            eff = (int)((int64_t)8 * cus / per_split);
-            if (eff < 1) eff = 1;
-        }
-    }
+    const int eff = decode_effective_splits(a->B, a->HKV, a->D, a->splits);
     p.splits = eff;
     p.logit_splits = a->splits;
     p.sm_scale = a->sm_scale; p.logit_cap = a->logit_cap;
@@ -1575,10 +1587,7 @@ extern "C" int sglk_decode_attention(const sglk_decode_attention_args* a, void* 
         }                                                                                                          \
         SGLK_CHECK_LAUNCH("decode_attention");                                                                     \
         if (p.direct) return SGLK_OK;                                                                              \
-        hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)a->B, (unsigned)a->HQ), dim3(256), 0, s, a->attn_logits,    \
-                           (unsigned short*)a->o, a->o_stride[0], a->o_stride[1], a->HQ, eff, a->splits, a->DV);   \
-        SGLK_CHECK_LAUNCH("decode_attention(merge)");                                                              \
-        return SGLK_OK;                                                                                            \
+        return launch_decode_merge(a->attn_logits, a->o, a->o_stride[0], a->o_stride[1], a->B, a->HQ, eff, a->splits, a->DV, s); \
     }
     DEC_CASE(576, 512)
     DEC_CASE(128, 128)

@@ -29,17 +29,6 @@ namespace bmm8 {
 
 constexpr int kRing = 4;   // 64-k weight steps in flight per wave
 
-SGLK_DEV bf16x8 cvt8(unsigned lo, unsigned hi) {
-    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
-    const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
-    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
-    const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
-    bf16x8 r;
-    r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1];
-    r[4] = c[0]; r[5] = c[1]; r[6] = d[0]; r[7] = d[1];
-    return r;
-}
-
 // flags: bit 0 = x may be read in 16-byte vectors, bit 1 = out may be written in 8-byte vectors (pointer and strides aligned)
 template <int MT, bool PACKED>
 __global__ __launch_bounds__(256) void bmm_heads_fp8_kernel(const uint16_t* __restrict__ x, int64_t x_sb, int64_t x_sh,

@@ -73,6 +73,18 @@ SGLK_DEV unsigned pack_bf16x2(float lo, float hi) {
     return __builtin_bit_cast(unsigned, v);
 }
 
+// 8 fp8 (e4m3fn) bytes -> 8 bf16, exactly (v_cvt_scalef32_pk_bf16_fp8 at scale 1.0: tools/probe/cvt_probe.hip), in byte order
+SGLK_DEV bf16x8 cvt8(unsigned lo, unsigned hi) {
+    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
+    const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
+    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
+    const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+    bf16x8 r;
+    r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1];
+    r[4] = c[0]; r[5] = c[1]; r[6] = d[0]; r[7] = d[1];
+    return r;
+}
+
 // 16 bytes of a weight stream.  NT: the non-temporal policy, for weights that one workgroup reads once per call (MoE experts at decode
 // sizes): same-box A/B of fused_experts fp8, replayed and with rotating weight copies alike (profiles/r03_ab_nt_weights.txt): 7-10 % less
 // time from 16 tokens on, nothing at 4, 13 % MORE at one token -- the launcher decides (MoeGemmParams::w_nt).  The bf16 mid kernel's

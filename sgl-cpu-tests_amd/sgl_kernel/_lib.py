@@ -141,6 +141,11 @@ OUT_BF16, OUT_F16, OUT_F32 = 0, 1, 2
 
 # symbol -> (restype, argtypes); every symbol include/sglk.h declares must be listed here
 # (tests/test_cabi_symbols.py checks the two against each other)
+class DecodeAttentionFp8kvArgs(ctypes.Structure):
+    """Mirror of `sglk_decode_attention_fp8kv_args`: the decode args plus the two cache scales."""
+    _fields_ = DecodeAttentionArgs._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float)]
+
+
 _SIGNATURES = {
     "sglk_version": (ctypes.c_int, []),
     "sglk_last_error": (ctypes.c_char_p, []),
@@ -222,6 +227,7 @@ _SIGNATURES = {
     "sglk_extend_attention": (ctypes.c_int, [ctypes.POINTER(ExtendAttentionArgs), ctypes.c_void_p]),
     "sglk_flash_attn_varlen": (ctypes.c_int, [ctypes.POINTER(FlashAttnVarlenArgs), ctypes.c_void_p]),
     "sglk_decode_attention": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionArgs), ctypes.c_void_p]),
+    "sglk_decode_attention_fp8kv": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionFp8kvArgs), ctypes.c_void_p]),
     "sglk_stage_timer_create": (ctypes.c_void_p, [ctypes.c_int32]),
     "sglk_stage_timer_destroy": (None, [ctypes.c_void_p]),
     "sglk_stage_timer_reset": (None, [ctypes.c_void_p]),

@@ -1,5 +1,6 @@
 """torch.library registration of the sgl_kernel operators (reference signatures) over the sglk C-ABI."""
 import ctypes
+import math
 import os
 
 import torch
@@ -998,34 +999,71 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
 _impl("flash_attn_varlen_func", flash_attn_varlen_func)
 
 
-def decode_attention_cpu(query, k_buffer, v_buffer, output, key, value, loc, attn_logits, req_to_token, b_req_idx,
-                         b_seq_len, sm_scale, logit_cap):
-    for t, n in ((query, "query"), (k_buffer, "k_buffer"), (v_buffer, "v_buffer"), (output, "output"), (key, "key"),
-                 (value, "value")):
-        _thd(t, "decode_attention: " + n)
+def _decode_args(cls, what, query, k_buffer, v_buffer, output, key, value, loc, attn_logits, req_to_token, b_req_idx,
+                 b_seq_len, sm_scale, logit_cap, **scales):
+    """Shape checks and the args struct shared by decode_attention_cpu and decode_attention_fp8kv; the index tensors it
+    converts are returned too, so that they outlive the launch."""
     B, HQ, D = query.shape
     HKV, DV = k_buffer.shape[1], v_buffer.shape[2]
     if tuple(output.shape) != (B, HQ, DV) or tuple(key.shape) != (B, HKV, D) or tuple(value.shape) != (B, HKV, DV):
-        raise RuntimeError("decode_attention: shape mismatch")
+        raise RuntimeError(f"{what}: shape mismatch")
     if attn_logits.dim() != 4 or attn_logits.dtype != torch.float32 or not attn_logits.is_contiguous() \
             or attn_logits.shape[0] != B or attn_logits.shape[1] != HQ or attn_logits.shape[3] != DV + 1:
-        raise RuntimeError("decode_attention: attn_logits must be contiguous f32 [B, HQ, splits, DV+1]")
+        raise RuntimeError(f"{what}: attn_logits must be contiguous f32 [B, HQ, splits, DV+1]")
     if loc.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("decode_attention: loc must be int32/int64")
-    rtt = _index2d(req_to_token, "decode_attention: req_to_token")
+        raise RuntimeError(f"{what}: loc must be int32/int64")
+    rtt = _index2d(req_to_token, f"{what}: req_to_token")
     req = b_req_idx.to(torch.int64).contiguous()
     seq = b_seq_len.to(torch.int64).contiguous()
     loc = loc.contiguous()
-    args = _lib.DecodeAttentionArgs(
+    args = cls(
         q=query.data_ptr(), k_buffer=k_buffer.data_ptr(), v_buffer=v_buffer.data_ptr(), o=output.data_ptr(),
         key=key.data_ptr(), value=value.data_ptr(), q_stride=_s2(query), k_buffer_stride=_s2(k_buffer),
         v_buffer_stride=_s2(v_buffer), o_stride=_s2(output), key_stride=_s2(key), value_stride=_s2(value),
         loc=loc.data_ptr(), loc_is64=int(loc.dtype == torch.int64), attn_logits=attn_logits.data_ptr(),
         req_to_token=rtt.data_ptr(), req_to_token_stride=rtt.stride(0), req_to_token_is64=int(rtt.dtype == torch.int64),
         b_req_idx=req.data_ptr(), b_seq_len=seq.data_ptr(), B=B, HQ=HQ, HKV=HKV, D=D, DV=DV,
-        splits=attn_logits.shape[2], sm_scale=float(sm_scale), logit_cap=float(logit_cap))
+        splits=attn_logits.shape[2], sm_scale=float(sm_scale), logit_cap=float(logit_cap), **scales)
+    return args, (rtt, req, seq, loc)
+
+
+def decode_attention_cpu(query, k_buffer, v_buffer, output, key, value, loc, attn_logits, req_to_token, b_req_idx,
+                         b_seq_len, sm_scale, logit_cap):
+    for t, n in ((query, "query"), (k_buffer, "k_buffer"), (v_buffer, "v_buffer"), (output, "output"), (key, "key"),
+                 (value, "value")):
+        _thd(t, "decode_attention: " + n)
+    args, keep = _decode_args(_lib.DecodeAttentionArgs, "decode_attention", query, k_buffer, v_buffer, output, key, value,
+                              loc, attn_logits, req_to_token, b_req_idx, b_seq_len, sm_scale, logit_cap)
     _lib.check(_lib.lib().sglk_decode_attention(ctypes.byref(args), _stream(query)), "decode_attention_cpu")
+
+
+# decode_attention_fp8kv: the project's own operator (no counterpart in the reference) -- decode_attention_cpu over a
+# float8_e4m3fn KV cache with one scale per tensor (include/sglk.h, csrc/attention_fp8kv.hip).  The scales travel by value: no
+# host synchronisation, the call can be captured in a graph.
+_DEF.define("decode_attention_fp8kv(Tensor query, Tensor(a!) k_buffer, Tensor(b!) v_buffer, Tensor(c!) output, "
+            "Tensor key, Tensor value, Tensor loc, Tensor(d!) attn_logits, Tensor req_to_token, Tensor b_req_idx, "
+            "Tensor b_seq_len, float sm_scale, float logit_cap, float k_scale, float v_scale) -> ()")
+
+
+def decode_attention_fp8kv(query, k_buffer, v_buffer, output, key, value, loc, attn_logits, req_to_token, b_req_idx,
+                           b_seq_len, sm_scale, logit_cap, k_scale, v_scale):
+    what = "decode_attention_fp8kv"
+    for t, n in ((query, "query"), (output, "output"), (key, "key"), (value, "value")):
+        _thd(t, f"{what}: {n}")
+    for t, n in ((k_buffer, "k_buffer"), (v_buffer, "v_buffer")):
+        if t.dim() != 3 or t.dtype != torch.float8_e4m3fn or t.stride(2) != 1:
+            raise RuntimeError(f"{what}: {n} must be a float8_e4m3fn [tokens, heads, dim] tensor with a contiguous last dim")
+    for v, n in ((k_scale, "k_scale"), (v_scale, "v_scale")):
+        if not (math.isfinite(v) and v > 0.0):
+            raise RuntimeError(f"{what}: {n} must be positive and finite, got {v}")
+    if k_scale != v_scale and v_buffer.data_ptr() == k_buffer.data_ptr() and v_buffer.stride() == k_buffer.stride():
+        raise RuntimeError(f"{what}: v_buffer aliases k_buffer, so k_scale and v_scale must be equal")
+    args, keep = _decode_args(_lib.DecodeAttentionFp8kvArgs, what, query, k_buffer, v_buffer, output, key, value, loc,
+                              attn_logits, req_to_token, b_req_idx, b_seq_len, sm_scale, logit_cap, k_scale=float(k_scale),
+                              v_scale=float(v_scale))
+    _lib.check(_lib.lib().sglk_decode_attention_fp8kv(ctypes.byref(args), _stream(query)), what)
 
 
 _impl("extend_attention_cpu", extend_attention_cpu, lambda a, args: a is args[3])
 _impl("decode_attention_cpu", decode_attention_cpu, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])
+_impl("decode_attention_fp8kv", decode_attention_fp8kv, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])

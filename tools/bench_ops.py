@@ -407,6 +407,42 @@ def bench_attn():
              roofline_frac_eager=round(byts / ms / 1e6 / PEAK_HBM, 4), bound="hbm")
 
 
+def bench_decode_fp8kv():
+    """decode_attention_fp8kv against decode_attention_cpu at the same shapes, in the same run: device time per call from
+    hipGraph replays, three alternating runs each (median reported, all kept).  bytes = the cache rows read."""
+    g = torch.Generator(device="cuda").manual_seed(4)
+    dt, f8 = torch.bfloat16, torch.float8_e4m3fn
+    for (B, HQ, HKV, D, DV, S, alias) in ((128, 22, 1, 576, 512, 4096, True), (64, 32, 4, 128, 128, 4096, False)):
+        total = B * S
+        q = torch.randn(B, HQ, D, device="cuda", generator=g).to(dt)
+        kb = torch.randn(total, HKV, D, device="cuda", generator=g).to(dt)
+        key = torch.randn(B, HKV, D, device="cuda", generator=g).to(dt)
+        vb = kb.narrow(2, 0, DV) if alias else torch.randn(total, HKV, DV, device="cuda", generator=g).to(dt)
+        val = key.narrow(2, 0, DV) if alias else torch.randn(B, HKV, DV, device="cuda", generator=g).to(dt)
+        kb8 = kb.to(f8)
+        vb8 = kb8.narrow(2, 0, DV) if alias else vb.to(f8)
+        o = torch.empty(B, HQ, DV, device="cuda", dtype=dt)
+        logits = torch.empty(B, HQ, 8, DV + 1, device="cuda", dtype=torch.float32)
+        rtt = torch.arange(total, device="cuda").view(B, S)
+        loc = rtt[:, -1].contiguous()
+        seq = torch.full((B,), S, device="cuda", dtype=torch.int64)
+        ridx = torch.arange(B, device="cuda")
+        sm = 1.0 / D ** 0.5
+        calls = {"bf16": lambda: ops.decode_attention_cpu(q, kb, vb, o, key, val, loc, logits, rtt, ridx, seq, sm, 0.0),
+                 "fp8kv": lambda: ops.decode_attention_fp8kv(q, kb8, vb8, o, key, val, loc, logits, rtt, ridx, seq, sm, 0.0, 1.0, 1.0)}
+        runs = {k: [] for k in calls}
+        for _ in range(3):
+            for k, f in calls.items():
+                runs[k].append(graph_ms(f))
+        dev = {k: sorted(v)[1] for k, v in runs.items()}
+        rows = total * HKV * (D if alias else D + DV)
+        for k, width in (("bf16", 2), ("fp8kv", 1)):
+            emit(op="decode_attention_" + k, B=B, HQ=HQ, HKV=HKV, D=D, DV=DV, seq=S, v_alias=alias, ms_device=round(dev[k], 4),
+                 ms_device_runs=[round(v, 4) for v in runs[k]], gbps=round(rows * width / dev[k] / 1e6, 1),
+                 roofline_frac=round(rows * width / dev[k] / 1e6 / PEAK_HBM, 4), bound="hbm",
+                 vs_bf16_device=round(dev["bf16"] / dev[k], 3))
+
+
 def bench_absorb():
     """qkv_proj_with_rope (/root/reference/test_absorb.py) at decode sizes: HBM-bound on the projection weights."""
     H, R, nope, rope, qlr, hidden = 22, 512, 128, 64, 1536, 7168
@@ -460,7 +496,7 @@ def bench_rows():
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
-    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "absorb": bench_absorb, "rows": bench_rows}
+    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "decode_fp8kv": bench_decode_fp8kv, "absorb": bench_absorb, "rows": bench_rows}
     for name, fn in table.items():
         if which in ("all", name):
             fn()
