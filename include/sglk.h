@@ -541,6 +541,42 @@ typedef struct {
 int sglk_decode_attention_fp8kv(const sglk_decode_attention_fp8kv_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * extend_attention_fp8kv      torch.ops.sgl_kernel.extend_attention_fp8kv: extend_attention over a float8_e4m3fn KV cache with
+ *                             one scale per tensor (the project's own operator; csrc/attention_extend_fp8kv.hip)
+ * 1. with out_cache_loc ([T] int32 or int64, T = extend tokens): k_buffer[out_cache_loc[t]] = e4m3(clamp(float(k_extend[t]) /
+ *    k_scale, -448, 448)), v_buffer likewise with v_scale -- the write kernel and rounding of decode_attention_fp8kv; needs
+ *    HBUF == HKV.  With out_cache_loc = NULL the buffers are only read.
+ * 2. for sequence b the keys / values are the paged prefix, float(k_buffer[page]) * k_scale and float(v_buffer[page]) * v_scale
+ *    (all visible), followed by the extend tokens k_extend / v_extend in bf16 as given (causal; never read back through their
+ *    quantised form).  fp32 softmax, bf16 P, fp32 accumulation, logit_cap as in extend_attention.
+ * q, k_extend, v_extend, o are bf16 (strides in elements); k_buffer / v_buffer are fp8 bytes: their strides and base pointers
+ * must be multiples of 16.  HBUF == HKV or 1.  Head dims 128/128 and 64/64; anything else is SGLK_ERR_SHAPE, and a rejected
+ * call changes no buffer.  T (used by the write only) must equal the number of rows of k_extend / v_extend.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void *q, *k_extend, *v_extend;
+    void *k_buffer, *v_buffer, *o;
+    int64_t q_stride[2], k_extend_stride[2], v_extend_stride[2], k_buffer_stride[2], v_buffer_stride[2], o_stride[2];
+    const void* req_to_tokens;       /* [B][L] int32 or int64 */
+    int64_t req_to_tokens_stride;
+    int32_t req_to_tokens_is64;
+    const int64_t* b_req_idx;        /* [B] */
+    const int64_t* b_seq_len;        /* [B] */
+    const int32_t* b_seq_len_extend; /* [B] */
+    const int32_t* b_start_loc_extend; /* [B] */
+    int32_t B, HQ, HKV, HBUF, D, DV, max_len_extend;
+    float sm_scale, logit_cap;
+    float k_scale, v_scale;
+    const void* out_cache_loc;       /* [T] int32 or int64, or NULL */
+    int32_t out_cache_loc_is64;
+    int32_t T;                       /* read only when out_cache_loc is set: the rows of k_extend / v_extend = the entries of
+                                        out_cache_loc.  The caller vouches for it: it is not checked against b_seq_len_extend,
+                                        and out_cache_loc is read for exactly T entries */
+} sglk_extend_attention_fp8kv_args;
+
+int sglk_extend_attention_fp8kv(const sglk_extend_attention_fp8kv_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Stages of fused_experts exposed for tests and profiling (same kernels the fused call launches).
  * moe_align: counting sort of the M*topk slots by expert (ids outside [0,E) dropped), stable in slot order.
  *   sorted_slot [M*topk] i32   slot = m*topk + j, grouped by expert

@@ -442,17 +442,22 @@ SGLK_DEV unsigned quant4(const unsigned short* src, float scale) {
     return (unsigned)w;
 }
 
+// T rows (decode: one per request; extend: every extend token) x H heads; a row of max(D, DV) columns takes TPR threads, a
+// workgroup 256 / TPR rows.
 __global__ __launch_bounds__(256) void kv_cache_write_fp8_kernel(unsigned char* k_buf, int64_t kb_s0, int64_t kb_s1, unsigned char* v_buf,
                                                                  int64_t vb_s0, int64_t vb_s1, const unsigned short* key, int64_t k_s0,
                                                                  int64_t k_s1, const unsigned short* value, int64_t v_s0, int64_t v_s1,
-                                                                 const void* loc, int loc_is64, int D, int DV, int alias, float k_scale,
-                                                                 float v_scale) {
-    const int b = blockIdx.x, h = blockIdx.y;
+                                                                 const void* loc, int loc_is64, int T, int D, int DV, int alias, float k_scale,
+                                                                 float v_scale, int tpr) {
+    const int r = threadIdx.x / tpr, x = threadIdx.x - r * tpr;
+    const int64_t b = (int64_t)blockIdx.x * (256 / tpr) + r;
+    const int h = blockIdx.y;
+    if (r >= 256 / tpr || b >= T) return;
     const int64_t tok = loc_is64 ? reinterpret_cast<const int64_t*>(loc)[b] : (int64_t)reinterpret_cast<const int*>(loc)[b];
-    for (int c = (alias ? DV : 0) + threadIdx.x * 4; c < D; c += 1024)
-        *reinterpret_cast<unsigned*>(k_buf + tok * kb_s0 + h * kb_s1 + c) = quant4(key + (int64_t)b * k_s0 + h * k_s1 + c, k_scale);
-    for (int c = threadIdx.x * 4; c < DV; c += 1024)
-        *reinterpret_cast<unsigned*>(v_buf + tok * vb_s0 + h * vb_s1 + c) = quant4(value + (int64_t)b * v_s0 + h * v_s1 + c, v_scale);
+    for (int c = (alias ? DV : 0) + x * 4; c < D; c += tpr * 4)
+        *reinterpret_cast<unsigned*>(k_buf + tok * kb_s0 + h * kb_s1 + c) = quant4(key + b * k_s0 + h * k_s1 + c, k_scale);
+    for (int c = x * 4; c < DV; c += tpr * 4)
+        *reinterpret_cast<unsigned*>(v_buf + tok * vb_s0 + h * vb_s1 + c) = quant4(value + b * v_s0 + h * v_s1 + c, v_scale);
 }
 
 template <int D, int DV, bool AL, int CT, int NDV, int KH>
@@ -482,6 +487,20 @@ int launch_by_group(const Params& p, int B, int group, int eff, hipStream_t s) {
 
 using namespace sglk;
 
+int sglk::attn::launch_kv_cache_write_fp8(void* k_buf, const int64_t* kb_stride, void* v_buf, const int64_t* vb_stride, const void* key,
+                                          const int64_t* key_stride, const void* value, const int64_t* value_stride, const void* loc,
+                                          int loc_is64, int T, int H, int D, int DV, int alias, float k_scale, float v_scale, hipStream_t s) {
+    if (T <= 0) return SGLK_OK;
+    const int w = ((D > DV ? D : DV) + 3) / 4;
+    const int tpr = w < 256 ? w : 256;
+    hipLaunchKernelGGL(attn8::kv_cache_write_fp8_kernel, dim3((unsigned)ceil_div(T, 256 / tpr), (unsigned)H), dim3(256), 0, s,
+                       (unsigned char*)k_buf, kb_stride[0], kb_stride[1], (unsigned char*)v_buf, vb_stride[0], vb_stride[1],
+                       (const unsigned short*)key, key_stride[0], key_stride[1], (const unsigned short*)value, value_stride[0],
+                       value_stride[1], loc, loc_is64, T, D, DV, alias, k_scale, v_scale, tpr);
+    SGLK_CHECK_LAUNCH("fp8 kv cache write");
+    return SGLK_OK;
+}
+
 extern "C" int sglk_decode_attention_fp8kv(const sglk_decode_attention_fp8kv_args* a, void* stream) {
     SGLK_REQUIRE(a, SGLK_ERR_INVALID, "decode_attention_fp8kv: null args");
     SGLK_REQUIRE(a->B >= 0 && a->HQ > 0 && a->HKV > 0 && a->HQ % a->HKV == 0, SGLK_ERR_INVALID,
@@ -508,12 +527,10 @@ extern "C" int sglk_decode_attention_fp8kv(const sglk_decode_attention_fp8kv_arg
     SGLK_REQUIRE(!alias || a->k_scale == a->v_scale, SGLK_ERR_INVALID,
                  "decode_attention_fp8kv: an aliased cache needs k_scale == v_scale (one byte cannot carry two scales)");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(attn8::kv_cache_write_fp8_kernel, dim3((unsigned)a->B, (unsigned)a->HKV), dim3(256), 0, s,
-                       (unsigned char*)a->k_buffer, a->k_buffer_stride[0], a->k_buffer_stride[1], (unsigned char*)a->v_buffer,
-                       a->v_buffer_stride[0], a->v_buffer_stride[1], (const unsigned short*)a->key, a->key_stride[0], a->key_stride[1],
-                       (const unsigned short*)a->value, a->value_stride[0], a->value_stride[1], a->loc, a->loc_is64, a->D, a->DV,
-                       alias ? 1 : 0, a->k_scale, a->v_scale);
-    SGLK_CHECK_LAUNCH("decode_attention_fp8kv(cache write)");
+    int rc = attn::launch_kv_cache_write_fp8(a->k_buffer, a->k_buffer_stride, a->v_buffer, a->v_buffer_stride, a->key, a->key_stride, a->value,
+                                             a->value_stride, a->loc, a->loc_is64, a->B, a->HKV, a->D, a->DV, alias ? 1 : 0, a->k_scale,
+                                             a->v_scale, s);
+    if (rc != SGLK_OK) return rc;
     const int eff = attn::decode_effective_splits(a->B, a->HKV, a->D, a->splits);
     attn8::Params p{};
     p.q = (const unsigned short*)a->q; p.k_buf = (const unsigned char*)a->k_buffer; p.v_buf = (const unsigned char*)a->v_buffer;
@@ -528,7 +545,6 @@ extern "C" int sglk_decode_attention_fp8kv(const sglk_decode_attention_fp8kv_arg
     p.o = (unsigned short*)a->o; p.o_s0 = a->o_stride[0]; p.o_s1 = a->o_stride[1];
     p.direct = (eff == 1 && a->o_stride[0] % 4 == 0 && a->o_stride[1] % 4 == 0 && ((uintptr_t)a->o % 8) == 0) ? 1 : 0;
     const int group = a->HQ / a->HKV;
-    int rc;
 #define DEC8_CASE(DD, DDV)                                                                                  \
     if (a->D == DD && a->DV == DDV)                                                                         \
         rc = alias ? attn8::launch_by_group<DD, DDV, true>(p, a->B, group, eff, s)                          \

@@ -146,6 +146,13 @@ class DecodeAttentionFp8kvArgs(ctypes.Structure):
     _fields_ = DecodeAttentionArgs._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float)]
 
 
+class ExtendAttentionFp8kvArgs(ctypes.Structure):
+    """Mirror of `sglk_extend_attention_fp8kv_args`: the extend args plus the cache scales and the optional write locations."""
+    _fields_ = ExtendAttentionArgs._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float),
+                                               ("out_cache_loc", ctypes.c_void_p), ("out_cache_loc_is64", ctypes.c_int32),
+                                               ("T", ctypes.c_int32)]
+
+
 _SIGNATURES = {
     "sglk_version": (ctypes.c_int, []),
     "sglk_last_error": (ctypes.c_char_p, []),
@@ -228,6 +235,7 @@ _SIGNATURES = {
     "sglk_flash_attn_varlen": (ctypes.c_int, [ctypes.POINTER(FlashAttnVarlenArgs), ctypes.c_void_p]),
     "sglk_decode_attention": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionArgs), ctypes.c_void_p]),
     "sglk_decode_attention_fp8kv": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionFp8kvArgs), ctypes.c_void_p]),
+    "sglk_extend_attention_fp8kv": (ctypes.c_int, [ctypes.POINTER(ExtendAttentionFp8kvArgs), ctypes.c_void_p]),
     "sglk_stage_timer_create": (ctypes.c_void_p, [ctypes.c_int32]),
     "sglk_stage_timer_destroy": (None, [ctypes.c_void_p]),
     "sglk_stage_timer_reset": (None, [ctypes.c_void_p]),

@@ -1064,6 +1064,59 @@ def decode_attention_fp8kv(query, k_buffer, v_buffer, output, key, value, loc, a
     _lib.check(_lib.lib().sglk_decode_attention_fp8kv(ctypes.byref(args), _stream(query)), what)
 
 
+# extend_attention_fp8kv: the project's own operator -- extend_attention_cpu over the float8_e4m3fn cache of
+# decode_attention_fp8kv (include/sglk.h, csrc/attention_extend_fp8kv.hip): the paged prefix is read as fp8 * scale, the extend
+# tokens in bf16 as given; with out_cache_loc their quantised rows are written into the cache (the decode operator's rounding).
+_DEF.define("extend_attention_fp8kv(Tensor q_extend, Tensor k_extend, Tensor v_extend, Tensor(a!) o_extend, "
+            "Tensor(b!) k_buffer, Tensor(c!) v_buffer, Tensor req_to_tokens, Tensor b_req_idx, Tensor b_seq_len, "
+            "Tensor b_seq_len_extend, Tensor b_start_loc_extend, int max_len_extend, float sm_scale, float logit_cap, "
+            "float k_scale, float v_scale, Tensor? out_cache_loc) -> ()")
+
+
+def extend_attention_fp8kv(q_extend, k_extend, v_extend, o_extend, k_buffer, v_buffer, req_to_tokens, b_req_idx, b_seq_len,
+                           b_seq_len_extend, b_start_loc_extend, max_len_extend, sm_scale, logit_cap, k_scale, v_scale,
+                           out_cache_loc):
+    what = "extend_attention_fp8kv"
+    for t, n in ((q_extend, "q_extend"), (k_extend, "k_extend"), (v_extend, "v_extend"), (o_extend, "o_extend")):
+        _thd(t, f"{what}: {n}")
+    for t, n in ((k_buffer, "k_buffer"), (v_buffer, "v_buffer")):
+        if t.dim() != 3 or t.dtype != torch.float8_e4m3fn or t.stride(2) != 1:
+            raise RuntimeError(f"{what}: {n} must be a float8_e4m3fn [tokens, heads, dim] tensor with a contiguous last dim")
+    for v, n in ((k_scale, "k_scale"), (v_scale, "v_scale")):
+        if not (math.isfinite(v) and v > 0.0):
+            raise RuntimeError(f"{what}: {n} must be positive and finite, got {v}")
+    T, HQ, D = q_extend.shape
+    HKV, DV = k_extend.shape[1], v_extend.shape[2]
+    if k_extend.shape[2] != D or k_buffer.shape[2] != D or v_buffer.shape[2] != DV or tuple(o_extend.shape) != (T, HQ, DV) \
+            or k_extend.shape[0] != T or tuple(v_extend.shape[:2]) != (T, HKV) or v_buffer.shape[1] != k_buffer.shape[1]:
+        raise RuntimeError(f"{what}: shape mismatch between q/k/v/o and the buffers")
+    loc = None
+    if out_cache_loc is not None:
+        if out_cache_loc.dtype not in (torch.int32, torch.int64) or tuple(out_cache_loc.shape) != (T,):
+            raise RuntimeError(f"{what}: out_cache_loc must be int32/int64 with one entry per extend token ({T})")
+        if k_buffer.shape[1] != HKV:
+            raise RuntimeError(f"{what}: the cache write needs buffers with {HKV} heads, got {k_buffer.shape[1]}")
+        loc = out_cache_loc.contiguous()
+    B = b_seq_len.shape[0]
+    rtt = _index2d(req_to_tokens, f"{what}: req_to_tokens")
+    req = b_req_idx.to(torch.int64).contiguous()
+    seq = b_seq_len.to(torch.int64).contiguous()
+    ext = b_seq_len_extend.to(torch.int32).contiguous()
+    start = b_start_loc_extend.to(torch.int32).contiguous()
+    args = _lib.ExtendAttentionFp8kvArgs(
+        q=q_extend.data_ptr(), k_extend=k_extend.data_ptr(), v_extend=v_extend.data_ptr(), k_buffer=k_buffer.data_ptr(),
+        v_buffer=v_buffer.data_ptr(), o=o_extend.data_ptr(), q_stride=_s2(q_extend), k_extend_stride=_s2(k_extend),
+        v_extend_stride=_s2(v_extend), k_buffer_stride=_s2(k_buffer), v_buffer_stride=_s2(v_buffer), o_stride=_s2(o_extend),
+        req_to_tokens=rtt.data_ptr(), req_to_tokens_stride=rtt.stride(0), req_to_tokens_is64=int(rtt.dtype == torch.int64),
+        b_req_idx=req.data_ptr(), b_seq_len=seq.data_ptr(), b_seq_len_extend=ext.data_ptr(),
+        b_start_loc_extend=start.data_ptr(), B=B, HQ=HQ, HKV=HKV, HBUF=k_buffer.shape[1], D=D, DV=DV,
+        max_len_extend=int(max_len_extend), sm_scale=float(sm_scale), logit_cap=float(logit_cap), k_scale=float(k_scale),
+        v_scale=float(v_scale), out_cache_loc=loc.data_ptr() if loc is not None else None,
+        out_cache_loc_is64=int(loc is not None and loc.dtype == torch.int64), T=T)
+    _lib.check(_lib.lib().sglk_extend_attention_fp8kv(ctypes.byref(args), _stream(q_extend)), what)
+
+
 _impl("extend_attention_cpu", extend_attention_cpu, lambda a, args: a is args[3])
+_impl("extend_attention_fp8kv", extend_attention_fp8kv, lambda a, args: a is args[3] or a is args[4] or a is args[5])
 _impl("decode_attention_cpu", decode_attention_cpu, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])
 _impl("decode_attention_fp8kv", decode_attention_fp8kv, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])

@@ -443,6 +443,52 @@ def bench_decode_fp8kv():
                  vs_bf16_device=round(dev["bf16"] / dev[k], 3))
 
 
+def bench_extend_fp8kv():
+    """extend_attention_fp8kv (a) against extend_attention_cpu on a bf16 copy of the same cache made outside the timed region (b),
+    and against what a user of the fp8 cache does without it, a torch dequantisation of the prefix rows to bf16 plus (b), both
+    timed (c) -- by page ids (gather + scatter: what a paged cache needs, and the dearest way) and by slices (possible only because
+    this bench's page table is contiguous: the cheapest): device time per call from hipGraph replays, three alternating runs each
+    (median reported, all kept).  The last shape has a prefix that is no multiple of the 64-key tile."""
+    g = torch.Generator(device="cuda").manual_seed(4)
+    dt, f8 = torch.bfloat16, torch.float8_e4m3fn
+    HQ, HKV, D = 32, 8, 128
+    for (B, P, E) in ((1, 0, 4096), (1, 8192, 512), (8, 2048, 256), (8, 2017, 256)):
+        S, T = P + E, B * E
+        q, k, v = (torch.randn(T, h, D, device="cuda", generator=g).to(dt) for h in (HQ, HKV, HKV))
+        kb8, vb8 = (torch.randn(B * S, HKV, D, device="cuda", generator=g).to(f8) for _ in range(2))
+        kb, vb = kb8.to(dt), vb8.to(dt)
+        kd, vd = torch.empty_like(kb), torch.empty_like(vb)
+        o = torch.empty(T, HQ, D, device="cuda", dtype=dt)
+        rtt = torch.arange(B * S, device="cuda").view(B, S)
+        pre = rtt[:, :P].reshape(-1)
+        seq = torch.full((B,), S, device="cuda", dtype=torch.int64)
+        ext = torch.full((B,), E, device="cuda", dtype=torch.int32)
+        start = torch.arange(B, device="cuda", dtype=torch.int32) * E
+        ridx = torch.arange(B, device="cuda")
+        sm = 1.0 / D ** 0.5
+        bf16 = lambda kk, vv: ops.extend_attention_cpu(q, k, v, o, kk, vv, rtt, ridx, seq, ext, start, E, sm, 0.0)
+
+        def today():
+            kd[pre] = kb8[pre].to(dt)
+            vd[pre] = vb8[pre].to(dt)
+            bf16(kd, vd)
+
+        def today_slices():
+            for dst, src in ((kd, kb8), (vd, vb8)):
+                dst.view(B, S, HKV, D)[:, :P] = src.view(B, S, HKV, D)[:, :P].to(dt)
+            bf16(kd, vd)
+        calls = {"fp8kv": lambda: ops.extend_attention_fp8kv(q, k, v, o, kb8, vb8, rtt, ridx, seq, ext, start, E, sm, 0.0, 1.0, 1.0, None),
+                 "bf16": lambda: bf16(kb, vb), "dequant_then_bf16": today, "dequant_slices_then_bf16": today_slices}
+        runs = {n: [] for n in calls}
+        for _ in range(3):
+            for n, f in calls.items():
+                runs[n].append(graph_ms(f))
+        dev = {n: sorted(r)[1] for n, r in runs.items()}
+        for n in calls:
+            emit(op="extend_attention_" + n, B=B, prefix=P, extend=E, HQ=HQ, HKV=HKV, D=D, ms_device=round(dev[n], 4),
+                 ms_device_runs=[round(r, 4) for r in runs[n]], vs_bf16_device=round(dev[n] / dev["bf16"], 3))
+
+
 def bench_absorb():
     """qkv_proj_with_rope (/root/reference/test_absorb.py) at decode sizes: HBM-bound on the projection weights."""
     H, R, nope, rope, qlr, hidden = 22, 512, 128, 64, 1536, 7168
@@ -496,7 +542,7 @@ def bench_rows():
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
-    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "decode_fp8kv": bench_decode_fp8kv, "absorb": bench_absorb, "rows": bench_rows}
+    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "decode_fp8kv": bench_decode_fp8kv, "extend_fp8kv": bench_extend_fp8kv, "absorb": bench_absorb, "rows": bench_rows}
     for name, fn in table.items():
         if which in ("all", name):
             fn()
