@@ -83,7 +83,17 @@ def close(got, ref):
 CASES = [(3, 22, 1, 576, 512, True, [65, 300, 1], torch.int64, 0.0, (1.0, 1.0)),
          (4, 16, 4, 128, 128, False, [63, 64, 130, 300], torch.int32, 30.0, (0.5, 2.0)),
          (2, 8, 2, 192, 128, False, [130, 65], torch.int64, 0.0, (1.0, 1.0)),
-         (3, 8, 8, 64, 64, False, [1, 300, 64], torch.int64, 0.0, (0.5, 2.0))]
+         (3, 8, 8, 64, 64, False, [1, 300, 64], torch.int64, 0.0, (0.5, 2.0)),
+         # The groups (HQ / HKV) at which launch_by_group takes another form, decode_fp8kv_kernel<D, DV, alias, CT, NDV, KH>: CT is 1
+         # up to 16 heads, 2 up to 32 and on wide heads (D >= 256), else 4; wide heads above 32 take two workgroups per kv head
+         (3, 24, 1, 128, 128, False, [63, 130, 300], torch.int64, 0.0, (0.5, 2.0)),    # <128, 128, false, 2, 1, 2>: CT = 2, narrow
+         (3, 40, 1, 128, 128, False, [64, 65, 300], torch.int32, 0.0, (0.5, 2.0)),     # <128, 128, false, 4, 1, 1>: third tile half full
+         (3, 64, 1, 128, 128, False, [1, 63, 130], torch.int64, 0.0, (0.5, 2.0)),      # <128, 128, false, 4, 1, 1>: four full tiles
+         (3, 33, 1, 64, 64, False, [65, 130, 300], torch.int64, 0.0, (0.5, 2.0)),      # <64, 64, false, 4, 1, 1>: one head in the third
+         (2, 24, 1, 192, 128, False, [130, 65], torch.int64, 0.0, (0.5, 2.0)),         # <192, 128, false, 2, 1, 2>
+         (3, 16, 1, 576, 512, True, [65, 300, 1], torch.int64, 0.0, (1.0, 1.0)),       # <576, 512, true, 1, 4, 2>: a full column tile
+         (3, 40, 1, 576, 512, True, [65, 300, 1], torch.int64, 0.0, (1.0, 1.0)),       # <576, 512, true, 2, 2, 2>, grid.y = 2: 32 + 8 heads
+         (3, 64, 1, 576, 512, True, [65, 300, 1], torch.int64, 0.0, (1.0, 1.0))]       # <576, 512, true, 2, 2, 2>, grid.y = 2: 32 + 32 heads
 
 
 @pytest.mark.parametrize("depth", [1, 8])
