@@ -45,7 +45,7 @@ enum {
     SGLK_W_BF16 = 0,
     SGLK_W_FP8_E4M3 = 1,
     SGLK_W_INT8 = 2,
-    SGLK_W_MXFP4 = 3   /* E2M1 pairs in bytes + E8M0 scales per 32 (sglk_mxfp4_scaled_mm only) */
+    SGLK_W_MXFP4 = 3   /* E2M1 pairs in bytes + E8M0 scales per 32 (sglk_mxfp4_scaled_mm, sglk_fused_experts) */
 };
 
 /* output element types of the dense GEMM entry points */
@@ -96,6 +96,11 @@ int sglk_unpack_weight(const void* src, void* dst, int64_t batch, int64_t rows, 
  * wtype   SGLK_W_FP8_E4M3: W8A16, w*_scale f32 [E][ceil(rows/block_n)][ceil(cols/block_k)], block_k == 128
  *         SGLK_W_BF16    : scales ignored
  *         SGLK_W_INT8    : W8A8 dynamic per-token activation quant, w1_scale [E][2N], w2_scale [E][K]
+ *         SGLK_W_MXFP4   : W4A16, w1 [E][2N][K/2] and w2 [E][K][N/2] bytes of two E2M1 codes (element 2i in the low nibble),
+ *                          w1_scale / w2_scale point at E8M0 BYTES [E][2N][K/32] / [E][K][N/32], row-major (one per 32
+ *                          consecutive elements of a row; the packed scale order is not taken).  K % 128 == 0 and
+ *                          N % 128 == 0, else SGLK_ERR_SHAPE; `packed`, block_n / block_k are ignored, flags must be 0;
+ *                          sglk_moe_block does not take this type
  * packed  bit 0: w1 is in sglk_pack_weight order, bit 1: w2 is (reference `is_vnni=True` = 3 when both shapes can be
  *         packed); 0: plain row-major.  The tuned fp8 kernels need both bits; anything else runs the generic engine
  * topk_weights [M][topk] f32, topk_ids [M][topk] i32
@@ -151,7 +156,8 @@ enum {
     SGLK_PATH_ROUTE_ALIGN = 0x20000,  /* sglk_moe_block: router + align ran as one launch */
     SGLK_PATH_SHARED_FOLDED = 0x40000,/* sglk_moe_block: routed combine folded into the shared expert's last launch */
     SGLK_PATH_SPLIT = 0x80000,        /* W8A16 with the activations as two exact e4m3 terms on the scaled fp8 MFMA */
-    SGLK_PATH_INLINE_ALIGN = 0x100000 /* at most 32 slots: no moe_align launch, the GEMM workgroups sort the ids themselves */
+    SGLK_PATH_INLINE_ALIGN = 0x100000,/* at most 32 slots: no moe_align launch, the GEMM workgroups sort the ids themselves */
+    SGLK_PATH_MXFP4 = 0x200000        /* MX-fp4 experts on the fp4 matrix cores (moe_gemm_mxfp4.hip); tile = 32 or 128 slots */
 };
 
 size_t sglk_fused_experts_workspace_bytes(int32_t M, int32_t N, int32_t K, int32_t E, int32_t topk, int32_t wtype);

@@ -65,6 +65,7 @@ void read_env() {
     k.attn_pp = env_int("SGLK_ATTN_PP", -1);
     k.mxfp4_native = env_int("SGLK_MXFP4_NATIVE", -1);
     k.mxfp4_rt = env_int("SGLK_MXFP4_RT", 4);
+    k.mxfp4_moe_tile = env_int("SGLK_MXFP4_MOE_TILE", 0);
     k.no_pack_on_the_fly = env_set("SGLK_NO_PACK_ON_THE_FLY");
     k.pack_min_rows = env_int("SGLK_PACK_MIN_ROWS", 0);
     k.inline_align_max = env_int("SGLK_INLINE_ALIGN_MAX", 16);

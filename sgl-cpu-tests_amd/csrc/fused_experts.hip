@@ -92,7 +92,8 @@ Workspace plan_workspace(int M, int N, int K, int E, int topk, int wtype, int fl
     w.tickets = take(16 * sizeof(int));
     w.ic1 = take((size_t)S * N * (wtype == SGLK_W_INT8 ? 4 : 2));   // W8A8 keeps SiLU*mul in fp32 until it is quantised
     w.ic2 = take((size_t)S * K * 2);
-    if (wtype == SGLK_W_FP8_E4M3 && !(flags & SGLK_MOE_FP8_ACT)) {   // two-term split of `hidden` (ic1's split rows take ic1's own place)
+    // two-term split of `hidden` (ic1's split rows take ic1's own place); MX-fp4 experts (W4A16) use the same plan
+    if ((wtype == SGLK_W_FP8_E4M3 && !(flags & SGLK_MOE_FP8_ACT)) || wtype == SGLK_W_MXFP4) {
         w.xq = take((size_t)M * 2 * K);
         w.xs = take((size_t)M * align_up(K / 128, 4));
         w.ic1s = take((size_t)S * align_up(N / 128, 4));
@@ -180,6 +181,97 @@ extern "C" size_t sglk_fused_experts_workspace_bytes_ex(int32_t M, int32_t N, in
 }
 
 namespace {
+// MX-fp4 experts (W4A16), weights and E8M0 scales as stored: split of `hidden` -> align -> GEMM-1 (+ SiLU*mul + the split of
+// ic1 in its epilogue) -> GEMM-2 (* routing weight) -> combine, all on moe_gemm_mxfp4.hip.  Shapes outside K % 128 == 0,
+// N % 128 == 0 are refused: there is no generic-engine form of this weight type.
+int fused_experts_mxfp4(const sglk_fused_experts_args* a, hipStream_t s) {
+    const int M = a->M, N = a->N, K = a->K, E = a->E, topk = a->topk;
+    SGLK_REQUIRE(a->w1_scale && a->w2_scale, SGLK_ERR_INVALID, "fused_experts: mxfp4 needs w1_scale [E,2N,K/32] and w2_scale [E,K,N/32] (E8M0 bytes)");
+    SGLK_REQUIRE(K % 128 == 0 && N % 128 == 0, SGLK_ERR_SHAPE, "fused_experts(mxfp4): K (%d) and N (%d) must be multiples of 128", K, N);
+    SGLK_REQUIRE(a->flags == 0, SGLK_ERR_INVALID, "fused_experts(mxfp4): flags 0x%x do not apply to this weight type", a->flags);
+    SGLK_REQUIRE(((uintptr_t)a->w1 % 16) == 0 && ((uintptr_t)a->w2 % 16) == 0 && ((uintptr_t)a->out % 2) == 0 && ((uintptr_t)a->hidden % 2) == 0,
+                 SGLK_ERR_INVALID, "fused_experts: misaligned");
+    const Workspace w = plan_workspace(M, N, K, E, topk, a->wtype, 0);
+    SGLK_REQUIRE(a->workspace_bytes >= w.total, SGLK_ERR_WORKSPACE, "fused_experts: workspace %zu < required %zu", a->workspace_bytes, w.total);
+    SGLK_REQUIRE(((uintptr_t)a->workspace % 256) == 0, SGLK_ERR_INVALID, "fused_experts: workspace must be 256-B aligned");
+    if (M == 0) return SGLK_OK;
+    unsigned char* ws = (unsigned char*)a->workspace;
+    int* sorted_slot = (int*)(ws + w.sorted_slot);
+    int* tile_info = (int*)(ws + w.tile_info);
+    int* num_tiles = (int*)(ws + w.num_tiles);
+    uint8_t* xq = ws + w.xq;
+    uint8_t* xs = ws + w.xs;
+    uint8_t* ic1q = ws + w.ic1;                    // split rows [position][hi N | lo N]: the bf16 ic1's footprint
+    uint8_t* ic1s = ws + w.ic1s;
+    uint16_t* ic2 = (uint16_t*)(ws + w.ic2);
+    const int64_t xs_stride = (int64_t)align_up(K / 128, 4), ic1s_stride = (int64_t)align_up(N / 128, 4);
+    StageTimer* tm = (StageTimer*)a->stage_timer;
+    if (tm && tm->calls >= tm->max_calls) tm = nullptr;
+    const int call = tm ? tm->calls++ : 0;
+    auto mark = [&](int i) {
+        if (tm) hipEventRecord(tm->at(call, i), s);
+    };
+    const int tile_m = mxfp4_moe_tile(M, E, topk);
+    const int max_tiles = sglk_moe_max_tiles(M, E, topk, tile_m);
+    mark(0);
+    int rc = launch_split_mxfp4_rows((const uint16_t*)a->hidden, a->hidden_stride, xq, 2 * (int64_t)K, xs, xs_stride, M, K, s);
+    if (rc != SGLK_OK) return rc;
+    rc = launch_moe_align_split(a->topk_ids, M, E, topk, tile_m, sorted_slot, (int*)(ws + w.expert_off), tile_info, num_tiles, 0, nullptr,
+                                nullptr, ws + w.align_ws, w.sorted_slot - w.align_ws, s);
+    if (rc != SGLK_OK) return rc;
+    mark(1);
+    Fp4MoeParams g1{};
+    g1.xq = xq;
+    g1.x_stride = 2 * (int64_t)K;
+    g1.x_rows = M;
+    g1.xs = xs;
+    g1.xs_stride = xs_stride;
+    g1.sorted_slot = sorted_slot;
+    g1.topk = topk;
+    g1.w = (const uint8_t*)a->w1;
+    g1.w_expert_stride = (int64_t)2 * N * (K / 2);
+    g1.ws = (const uint8_t*)a->w1_scale;
+    g1.ws_expert_stride = (int64_t)2 * N * (K / 32);
+    g1.C = K;
+    g1.n_half = N;
+    g1.tile_info = (const int4*)tile_info;
+    g1.num_tiles = num_tiles;
+    g1.n_tiles = N / 128;
+    g1.out_q = ic1q;
+    g1.out_q_stride = 2 * (int64_t)N;
+    g1.out_s = ic1s;
+    g1.out_s_stride = ic1s_stride;
+    rc = launch_moe_gemm_mxfp4(MODE_GATE_UP, tile_m, g1, max_tiles, s);
+    if (rc != SGLK_OK) return rc;
+    mark(2);
+    Fp4MoeParams g2{};
+    g2.xq = ic1q;
+    g2.x_stride = 2 * (int64_t)N;
+    g2.x_rows = (int64_t)M * topk;
+    g2.xs = ic1s;
+    g2.xs_stride = ic1s_stride;
+    g2.sorted_slot = sorted_slot;
+    g2.topk = topk;
+    g2.w = (const uint8_t*)a->w2;
+    g2.w_expert_stride = (int64_t)K * (N / 2);
+    g2.ws = (const uint8_t*)a->w2_scale;
+    g2.ws_expert_stride = (int64_t)K * (N / 32);
+    g2.C = N;
+    g2.tile_info = (const int4*)tile_info;
+    g2.num_tiles = num_tiles;
+    g2.n_tiles = K / 128;
+    g2.out = ic2;
+    g2.out_stride = K;
+    g2.topk_weights = a->topk_weights;
+    rc = launch_moe_gemm_mxfp4(MODE_DOWN, tile_m, g2, max_tiles, s);
+    if (rc != SGLK_OK) return rc;
+    mark(3);
+    rc = launch_moe_combine(ic2, a->topk_ids, (uint16_t*)a->out, a->out_stride, M, K, E, topk, s);
+    mark(4);
+    if (a->path_taken) *a->path_taken = (tile_m & SGLK_PATH_TILE_MASK) | SGLK_PATH_MXFP4;
+    return rc;
+}
+
 // router inputs of sglk_moe_block: topk_weights / topk_ids of the experts' args are then OUTPUTS of the call
 struct RouteArgs {
     const void* gating;
@@ -204,9 +296,13 @@ int fused_experts_impl(const sglk_fused_experts_args* a, void* stream, const Rou
                  "fused_experts: null pointer");
     SGLK_REQUIRE(a->hidden_stride >= K && a->out_stride >= K, SGLK_ERR_INVALID, "fused_experts: row stride < K");
     SGLK_REQUIRE((int64_t)M * topk * (int64_t)(K > N ? K : N) < (1ll << 40), SGLK_ERR_SHAPE, "fused_experts: too large");
-    SGLK_REQUIRE(a->wtype == SGLK_W_BF16 || a->wtype == SGLK_W_FP8_E4M3 || a->wtype == SGLK_W_INT8, SGLK_ERR_INVALID,
-                 "fused_experts: unknown weight type %d", a->wtype);
+    SGLK_REQUIRE(a->wtype == SGLK_W_BF16 || a->wtype == SGLK_W_FP8_E4M3 || a->wtype == SGLK_W_INT8 || a->wtype == SGLK_W_MXFP4,
+                 SGLK_ERR_INVALID, "fused_experts: unknown weight type %d", a->wtype);
     hipStream_t s = (hipStream_t)stream;
+    if (a->wtype == SGLK_W_MXFP4) {
+        SGLK_REQUIRE(!route && !shared, SGLK_ERR_INVALID, "moe_block: MX-fp4 experts are not supported");
+        return fused_experts_mxfp4(a, s);
+    }
 
     if (a->wtype == SGLK_W_FP8_E4M3) {
         SGLK_REQUIRE(a->w1_scale && a->w2_scale, SGLK_ERR_INVALID, "fused_experts: fp8 needs w1_scale and w2_scale");

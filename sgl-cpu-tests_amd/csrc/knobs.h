@@ -43,6 +43,7 @@ struct Knobs {
     int no_pack_on_the_fly = 0;  // SGLK_NO_PACK_ON_THE_FLY: row-major dense weights stay on the generic engine at every M (A/B)
     int mxfp4_rt = 4;            // SGLK_MXFP4_RT: 32-row tiles per wave of the fp4-MFMA kernel (4 / 2; A/B)
     int mxfp4_native = -1;       // SGLK_MXFP4_NATIVE: 1 / 0 = fp4-MFMA kernel for every legal shape / never; unset = by tile count
+    int mxfp4_moe_tile = 0;      // SGLK_MXFP4_MOE_TILE: slots per tile of the MX-fp4 fused_experts kernels (32 / 128); 0 = by rows per expert
     int attn_order = -1;         // SGLK_ATTN_ORDER: A/B override of the extend-attention dispatch order
     int inline_align_max = 16;   // SGLK_INLINE_ALIGN_MAX: fused_experts with at most this many slots (<= 32) sorts the ids in the GEMM kernels, no moe_align launch; 0 = never (A/B)
     bool no_block_fold = false;  // SGLK_NO_BLOCK_FOLD: sglk_moe_block runs router / align / combine / shared expert unfused (A/B)

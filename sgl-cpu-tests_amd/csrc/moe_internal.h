@@ -309,6 +309,37 @@ bool mxfp4_native_ok(int M, int N, int K, const void* x, int64_t x_stride, const
 int launch_gemm_mxfp4_native(const void* x, int64_t x_stride, const void* wq, const void* scales, int scale_packed, const float* bias,
                              void* out, int64_t out_stride, int M, int N, int K, void* workspace, hipStream_t stream);
 
+// ---- fused_experts with MX-fp4 (W4A16) expert weights as stored (moe_gemm_mxfp4.hip) -------------------------------------------
+struct Fp4MoeParams {
+    const uint8_t* xq;            // split activations [row][hi C | lo C] e4m3, natural k order (GATE_UP: rows of hidden; DOWN: ic1 by position)
+    int64_t x_stride;             // bytes per row (>= 2 C)
+    int64_t x_rows;               // rows of xq (x_rows * x_stride < 4 GiB: the kernels address them by 32-bit offsets)
+    const uint8_t* xs;            // E8M0 byte per (row, 128-wide block), row stride xs_stride
+    int64_t xs_stride;
+    const int* sorted_slot;
+    int topk;
+    const uint8_t* w;             // [E][R][C / 2] E2M1 pairs, row-major (16-byte aligned)
+    int64_t w_expert_stride;      // bytes per expert
+    const uint8_t* ws;            // [E][R][C / 32] E8M0, row-major
+    int64_t ws_expert_stride;
+    int C;                        // reduction length (% 128 == 0)
+    int n_half;                   // GATE_UP: N
+    const int4* tile_info;        // tile_m = 32 or 128
+    const int* num_tiles;
+    int n_tiles;                  // GATE_UP: N / 128; DOWN: K / 128
+    uint8_t* out_q;               // GATE_UP: ic1 split rows [position][hi N | lo N]
+    int64_t out_q_stride;
+    uint8_t* out_s;               // GATE_UP: ic1 E8M0 bytes [position][out_s_stride]
+    int64_t out_s_stride;
+    uint16_t* out;                // DOWN: ic2 bf16 [slot][K]
+    int64_t out_stride;
+    const float* topk_weights;    // DOWN
+};
+int mxfp4_moe_tile(int M, int E, int topk);   // 32 or 128 slots per tile (SGLK_MXFP4_MOE_TILE forces)
+int launch_split_mxfp4_rows(const uint16_t* x, int64_t x_stride, uint8_t* q, int64_t q_stride, uint8_t* s, int64_t s_stride,
+                            int64_t rows, int cols, hipStream_t stream);
+int launch_moe_gemm_mxfp4(int mode, int tile_m, const Fp4MoeParams& p, int max_mtiles, hipStream_t stream);
+
 // moe_align with a second tile table: an expert's last tile lands in tile_info_b when it has at most tail_max rows
 // (tail_max <= 0: exactly sglk_moe_align)
 int launch_moe_align_split(const int32_t* topk_ids, int32_t M, int32_t E, int32_t topk, int32_t tile_m, int32_t* sorted_slot,

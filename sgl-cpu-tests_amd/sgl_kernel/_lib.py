@@ -5,12 +5,13 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGLK_LIB_PATH") or os.path.join(_HERE, "libsglk.so")   # override: developer A/B builds
 
-W_BF16, W_FP8_E4M3, W_INT8 = 0, 1, 2
+W_BF16, W_FP8_E4M3, W_INT8, W_MXFP4 = 0, 1, 2, 3
 MOE_FP8_ACT = 1                      # sglk_fused_experts_args.flags
 MOE_PACK_WEIGHTS = 2                 # row-major weights: re-tile them into the workspace, run the packed kernels
 PATH_TILE_MASK, PATH_FP8_ACT, PATH_TAILS_SPLIT, PATH_TAILS_AUX, PATH_PERSIST_G1, PATH_PERSIST_G2 = (
     0x3ff, 0x1000, 0x2000, 0x4000, 0x8000, 0x10000)
 PATH_ROUTE_ALIGN, PATH_SHARED_FOLDED, PATH_SPLIT, PATH_INLINE_ALIGN = 0x20000, 0x40000, 0x80000, 0x100000
+PATH_MXFP4 = 0x200000
 
 
 class FusedExpertsArgs(ctypes.Structure):

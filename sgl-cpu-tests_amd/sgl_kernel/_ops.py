@@ -216,10 +216,64 @@ def set_fp8_activations(on):
 
 # sglang.srt.layers.amx_utils.CPUQuantMethod values (shim in sgl-cpu-tests_amd/sglang)
 UNQUANT, INT8_W8A8, FP8_W8A16 = 0, 1, 2
+MXFP4_W4A16 = 4   # this project's own value (fused_experts_cpu.method only): MX-fp4 expert weights, W4A16
+
+
+def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace, w1_scale, w2_scale):
+    """w1 [E,2N,K/2] / w2 [E,K,N/2] uint8 (two E2M1 codes per byte), w*_scale uint8 E8M0 [E,2N,K/32] / [E,K,N/32], row-major
+    (oracle/gemm.py: mxfp4_quantize).  block_size and is_vnni do not apply: the kernels read the weights as stored."""
+    if hidden_states.dim() != 2 or w1.dim() != 3 or w2.dim() != 3 or hidden_states.dtype != torch.bfloat16:
+        raise RuntimeError("fused_experts(mxfp4): expect bfloat16 hidden [M,K], w1 [E,2N,K/2], w2 [E,K,N/2]")
+    M, K = hidden_states.shape
+    E, N2 = w1.shape[0], w1.shape[1]
+    N = N2 // 2
+    if w1.dtype != torch.uint8 or w2.dtype != torch.uint8:
+        raise RuntimeError(f"fused_experts: weights must be torch.uint8 for this mode (got {w1.dtype}, {w2.dtype})")
+    if w1_scale is None or w2_scale is None or w1_scale.dtype != torch.uint8 or w2_scale.dtype != torch.uint8:
+        raise RuntimeError("fused_experts(mxfp4): w1_scale and w2_scale must be uint8 E8M0 tensors")
+    if K % 128 != 0 or N % 128 != 0 or N2 != 2 * N:
+        raise RuntimeError(f"fused_experts(mxfp4): K ({K}) and N ({N}) must be multiples of 128")
+    if w1.shape[2] * 2 != K or tuple(w2.shape) != (E, K, N // 2):
+        raise RuntimeError(f"fused_experts(mxfp4): shape mismatch hidden {tuple(hidden_states.shape)} w1 {tuple(w1.shape)} "
+                           f"w2 {tuple(w2.shape)}")
+    if tuple(w1_scale.shape) != (E, N2, K // 32) or tuple(w2_scale.shape) != (E, K, N // 32):
+        raise RuntimeError(f"fused_experts(mxfp4): scales must be [E,2N,K/32] and [E,K,N/32] (got {tuple(w1_scale.shape)}, "
+                           f"{tuple(w2_scale.shape)})")
+    if topk_weights.shape != topk_ids.shape or topk_ids.dim() != 2 or topk_ids.shape[0] != M:
+        raise RuntimeError("fused_experts: topk_weights/topk_ids must both be [M, topk]")
+    topk = topk_ids.shape[1]
+    hidden_states_c = hidden_states if hidden_states.stride(1) == 1 else hidden_states.contiguous()
+    topk_weights = _f32c(topk_weights)
+    if topk_ids.dtype != torch.int32 or not topk_ids.is_contiguous():
+        topk_ids = topk_ids.to(torch.int32).contiguous()
+    w1, w2, w1_scale, w2_scale = w1.contiguous(), w2.contiguous(), w1_scale.contiguous(), w2_scale.contiguous()
+    out = hidden_states_c if (inplace and hidden_states_c is hidden_states) else torch.empty_like(hidden_states_c)
+    L = _lib.lib()
+    ws_bytes = L.sglk_fused_experts_workspace_bytes_ex(M, N, K, E, topk, _lib.W_MXFP4, 0)
+    ws = _workspace(ws_bytes, hidden_states.device)
+    path = ctypes.c_int32(0)
+    args = _lib.FusedExpertsArgs(
+        hidden=hidden_states_c.data_ptr(), hidden_stride=hidden_states_c.stride(0), out=out.data_ptr(), out_stride=out.stride(0),
+        w1=w1.data_ptr(), w2=w2.data_ptr(), w1_scale=w1_scale.data_ptr(), w2_scale=w2_scale.data_ptr(),
+        topk_weights=topk_weights.data_ptr(), topk_ids=topk_ids.data_ptr(), M=M, N=N, K=K, E=E, topk=topk, wtype=_lib.W_MXFP4,
+        packed=0, block_n=0, block_k=0, workspace=ws.data_ptr(), workspace_bytes=ws_bytes, stage_timer=_stage_timer,
+        aux_stream=None, aux_events=(ctypes.c_void_p * 2)(), flags=0, path_taken=ctypes.pointer(path))
+    rc = L.sglk_fused_experts(ctypes.byref(args), _stream(hidden_states))
+    _lib.check(rc, "fused_experts_cpu")
+    global last_path
+    last_path = path.value
+    if inplace and out is not hidden_states:
+        hidden_states.copy_(out)
+        return hidden_states
+    return out
 
 
 def _fused_experts(hidden_states, w1, w2, topk_weights, topk_ids, inplace, method, w1_scale, w2_scale,
                    block_size, a1_scale, a2_scale, is_vnni):
+    if int(method) == MXFP4_W4A16:
+        if a1_scale is not None or a2_scale is not None:
+            raise RuntimeError("fused_experts: static activation scales (a1_scale/a2_scale) are not supported")
+        return _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace, w1_scale, w2_scale)
     if hidden_states.dim() != 2 or w1.dim() != 3 or w2.dim() != 3:
         raise RuntimeError("fused_experts: expect hidden [M,K], w1 [E,2N,K], w2 [E,K,N]")
     if hidden_states.dtype != torch.bfloat16:
