@@ -547,6 +547,41 @@ typedef struct {
 int sglk_decode_attention_fp8kv(const sglk_decode_attention_fp8kv_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * decode_attention_multi      torch.ops.sgl_kernel.decode_attention_multi: decode_attention with Q new tokens per request in one
+ *                             pass over the cache (the verify step of speculative decoding; the project's own operator;
+ *                             csrc/attention_decode_multi.hip)
+ * B requests, T = B * Q rows: rows b * Q + t (t = 0 .. Q-1) of q [T][HQ][D], key [T][HKV][D], value [T][HKV][DV], o [T][HQ][DV]
+ * and loc [T] belong to request b; attn_logits is [T][HQ][splits][DV+1] f32; the cache is bf16.
+ * 1. k_buffer[loc[r]] = key[r]; v_buffer[loc[r]] = value[r] for all T rows (bit-exact; with an aliased cache value wins in the
+ *    first DV columns),
+ * 2. b_seq_len[b] counts the Q new tokens: token t sits at position p = b_seq_len[b] - Q + t and attends to
+ *    req_to_token[b_req_idx[b]][0 .. p] over the cache as it stands after the write (the caller's page table names the new
+ *    rows); a token with p < 0 sees nothing and its row of o is zeros,
+ * 3. split partials and merge as in decode_attention.  Q = 1 computes what decode_attention computes.
+ * Head dims 576/512, 128/128, 192/128, 64/64 (anything else is SGLK_ERR_SHAPE before any launch); any HQ / HKV.  q and the
+ * caches must be 16-byte aligned with strides that are multiples of 8 elements.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* q;
+    void *k_buffer, *v_buffer, *o;
+    const void *key, *value;
+    int64_t q_stride[2], k_buffer_stride[2], v_buffer_stride[2], o_stride[2], key_stride[2], value_stride[2];
+    const void* loc;                 /* [B * Q] int32 or int64 */
+    int32_t loc_is64;
+    float* attn_logits;
+    const void* req_to_token;        /* [B][L] int32 or int64 */
+    int64_t req_to_token_stride;
+    int32_t req_to_token_is64;
+    const int64_t* b_req_idx;
+    const int64_t* b_seq_len;
+    int32_t B, HQ, HKV, D, DV, splits;   /* B = requests */
+    float sm_scale, logit_cap;
+    int32_t Q;                       /* query tokens per request, >= 1 */
+} sglk_decode_attention_multi_args;
+
+int sglk_decode_attention_multi(const sglk_decode_attention_multi_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * extend_attention_fp8kv      torch.ops.sgl_kernel.extend_attention_fp8kv: extend_attention over a float8_e4m3fn KV cache with
  *                             one scale per tensor (the project's own operator; csrc/attention_extend_fp8kv.hip)
  * 1. with out_cache_loc ([T] int32 or int64, T = extend tokens): k_buffer[out_cache_loc[t]] = e4m3(clamp(float(k_extend[t]) /

@@ -334,14 +334,6 @@ __global__ __launch_bounds__(256) void kv_cache_write_kernel(unsigned short* k_b
     for (int c = threadIdx.x; c < DV; c += 256) v_buf[tok * vb_s0 + h * vb_s1 + c] = value[(int64_t)b * v_s0 + h * v_s1 + c];
 }
 
-// A/B knobs of the decode kernel (compile time): images up to this size are double buffered; wave groups for wide heads
-#ifndef SGLK_DEC_DOUBLE_LIMIT
-#define SGLK_DEC_DOUBLE_LIMIT (150 * 1024)
-#endif
-#ifndef SGLK_DEC_KH_WIDE
-#define SGLK_DEC_KH_WIDE 2
-#endif
-
 struct DecodeParams {
     const unsigned short *q, *k_buf, *v_buf;
     int64_t q_s0, q_s1, kb_s0, kb_s1, vb_s0, vb_s1;
@@ -367,66 +359,6 @@ struct DecodeParams {
     int64_t key_s0, key_s1, val_s0, val_s1;
     int loc_is64, B, fold_write;
     int abl;                // developer build only (SGLK_ABL): 1 = no tile arithmetic, 2 = no row requests after the prologue
-};
-
-// LDS-DMA staging of one 64-key tile (no registers, asynchronous): the image is written linearly, 1 KiB per wave
-// instruction, and the 16-byte-chunk swizzle is applied to the SOURCE address.  Rows past `nkeys` re-read the last valid
-// row (finite data: their probabilities are exactly 0, but 0 * garbage must not be NaN).  Returns nothing to wait on:
-// the caller counts the instructions (kDmaPerThread) in its s_waitcnt vmcnt.
-template <int WIDTH, int THREADS>   // THREADS = the decode kernel's workgroup size (256 or 512)
-struct TileDma {
-    static constexpr int CH = WIDTH / 8;
-    static constexpr int N = (kKeys * CH + THREADS - 1) / THREADS;   // DMA instructions per wave per tile
-    static_assert((kKeys * CH) % THREADS == 0, "the image must be a whole number of workgroup-wide DMA rounds");
-    // Decode kernel: the cache rows (page-table entries) of a tile are themselves fetched by LDS-DMA -- ONE 256-byte instruction of
-    // one wave per tile, into a small ring of id tables -- a whole step before the tile's rows are requested, and the row
-    // requests read them from LDS.  (Per-lane lookups cost N loads and N registers per lane and tile; and loads retire in order,
-    // so a lookup queued behind the previous tile's rows could not be consumed before those had landed.)  Positions past `nkeys`
-    // repeat the last valid row.  An int64 table contributes its low words (cache rows are < 2^31).
-    SGLK_DEV static void lookup_dma(unsigned* ids, const KvSource& src, int p0, int nkeys, int lane) {
-        const int rr = lane < nkeys ? lane : nkeys - 1;
-        const unsigned char* g = reinterpret_cast<const unsigned char*>(src.page) + (int64_t)(p0 + rr) * (src.page_is64 ? 8 : 4);
-        __builtin_amdgcn_global_load_lds((dma_gptr_t)g, (dma_lptr_t)ids, 4, 0, 0);
-    }
-    template <int AUX>   // 2 = non-temporal: rows that one workgroup reads once need not stay in L2 / the Infinity Cache
-    SGLK_DEV static void issue_rows(unsigned char* lds, const KvSource& src, const unsigned* ids, int wave, int lane) {
-        constexpr int MASK = Swz<CH>::mask;
-        int tok[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) tok[i] = (int)ids[(i * THREADS + wave * 64 + lane) / CH];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const int c = i * THREADS + wave * 64 + lane;
-            const int row = c / CH, slot = c - row * CH;
-            const unsigned short* g = src.buf + (int64_t)tok[i] * src.buf_stride_tok + ((slot ^ (row & MASK)) << 3);
-            __builtin_amdgcn_global_load_lds((dma_gptr_t)g, (dma_lptr_t)(lds + (i * THREADS + wave * 64) * 16), 16, 0, AUX);
-        }
-    }
-    SGLK_DEV static void issue(unsigned char* lds, const KvSource& src, int p0, int nkeys, int wave, int lane) {
-        constexpr int MASK = Swz<CH>::mask;
-        constexpr int HALF = (N + 1) / 2;
-        // two passes per half: all row lookups first (independent loads, one wait), then the DMA instructions
-#pragma unroll
-        for (int h0 = 0; h0 < N; h0 += HALF) {
-            const unsigned short* g[HALF];
-#pragma unroll
-            for (int j = 0; j < HALF; ++j) {
-                const int i = h0 + j;
-                if (i < N) {
-                    const int c = i * THREADS + wave * 64 + lane;        // linear chunk of the image this lane fills
-                    const int row = c / CH, slot = c - row * CH;
-                    const int rr = row < nkeys ? row : nkeys - 1;
-                    g[j] = kv_row_paged(src, p0 + rr) + ((slot ^ (row & MASK)) << 3);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < HALF; ++j) {
-                const int i = h0 + j;
-                if (i < N)
-                    __builtin_amdgcn_global_load_lds((dma_gptr_t)g[j], (dma_lptr_t)(lds + (i * THREADS + wave * 64) * 16), 16, 0, 0);
-            }
-        }
-    }
 };
 
 // 8 waves = 2 key halves x CT column tiles (16 q heads each) x NDV slices of the value width (CT * NDV = 4): a wave computes
@@ -858,6 +790,17 @@ int sglk::attn::launch_decode_merge(const float* attn_logits, void* o, int64_t o
     hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)B, (unsigned)HQ), dim3(256), 0, stream, attn_logits, (unsigned short*)o,
                        o_s0, o_s1, HQ, eff, splits, DV);
     SGLK_CHECK_LAUNCH("decode_attention(merge)");
+    return SGLK_OK;
+}
+
+int sglk::attn::launch_kv_cache_write(void* k_buf, const int64_t* kb_stride, void* v_buf, const int64_t* vb_stride, const void* key,
+                                      const int64_t* key_stride, const void* value, const int64_t* value_stride, const void* loc,
+                                      int loc_is64, int T, int H, int D, int DV, hipStream_t stream) {
+    if (T <= 0) return SGLK_OK;
+    hipLaunchKernelGGL(kv_cache_write_kernel, dim3((unsigned)T, (unsigned)H), dim3(256), 0, stream, (unsigned short*)k_buf, kb_stride[0],
+                       kb_stride[1], (unsigned short*)v_buf, vb_stride[0], vb_stride[1], (const unsigned short*)key, key_stride[0],
+                       key_stride[1], (const unsigned short*)value, value_stride[0], value_stride[1], loc, loc_is64, T, H, D, DV);
+    SGLK_CHECK_LAUNCH("kv cache write");
     return SGLK_OK;
 }
 

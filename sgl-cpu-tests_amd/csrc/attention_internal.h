@@ -13,6 +13,12 @@ int decode_effective_splits(int B, int HKV, int D, int splits);
 int launch_decode_merge(const float* attn_logits, void* o, int64_t o_s0, int64_t o_s1, int B, int HQ, int eff, int splits, int DV,
                         hipStream_t stream);
 
+// kv_cache_write_kernel (attention.hip) over T rows x H heads: k_buf[loc[t]][h] = key[t][h], v_buf likewise, bit-exact; strides
+// {token, head} in elements.  V after K in program order: with an aliased cache `value` wins in the first DV columns.
+int launch_kv_cache_write(void* k_buf, const int64_t* kb_stride, void* v_buf, const int64_t* vb_stride, const void* key,
+                          const int64_t* key_stride, const void* value, const int64_t* value_stride, const void* loc, int loc_is64,
+                          int T, int H, int D, int DV, hipStream_t stream);
+
 // quantising write of the fp8-cache operators (attention_fp8kv.hip): k_buf[loc[t]][h] = e4m3(clamp(key[t][h] / k_scale, +-448)) for
 // T rows x H heads, v_buf likewise; cache strides {token, head} in bytes, key / value strides in elements
 int launch_kv_cache_write_fp8(void* k_buf, const int64_t* kb_stride, void* v_buf, const int64_t* vb_stride, const void* key,
@@ -412,6 +418,74 @@ struct HalfDma {
 #pragma unroll
         for (int i = 0; i < N; ++i)
             __builtin_amdgcn_global_load_lds((dma_gptr_t)g[i], (dma_lptr_t)(lds + (grp * (32 * CH) + i * 256 + wv * 64) * 16), 16, 0, 0);
+    }
+};
+
+// A/B knobs of the decode kernel (compile time): images up to this size are double buffered; wave groups for wide heads
+#ifndef SGLK_DEC_DOUBLE_LIMIT
+#define SGLK_DEC_DOUBLE_LIMIT (150 * 1024)
+#endif
+#ifndef SGLK_DEC_KH_WIDE
+#define SGLK_DEC_KH_WIDE 2
+#endif
+
+// LDS-DMA staging of one 64-key tile (no registers, asynchronous): the image is written linearly, 1 KiB per wave
+// instruction, and the 16-byte-chunk swizzle is applied to the SOURCE address.  Rows past `nkeys` re-read the last valid
+// row (finite data: their probabilities are exactly 0, but 0 * garbage must not be NaN).  Returns nothing to wait on:
+// the caller counts the instructions (kDmaPerThread) in its s_waitcnt vmcnt.
+template <int WIDTH, int THREADS>   // THREADS = the decode kernel's workgroup size (256 or 512)
+struct TileDma {
+    static constexpr int CH = WIDTH / 8;
+    static constexpr int N = (kKeys * CH + THREADS - 1) / THREADS;   // DMA instructions per wave per tile
+    static_assert((kKeys * CH) % THREADS == 0, "the image must be a whole number of workgroup-wide DMA rounds");
+    // Decode kernel: the cache rows (page-table entries) of a tile are themselves fetched by LDS-DMA -- ONE 256-byte instruction of
+    // one wave per tile, into a small ring of id tables -- a whole step before the tile's rows are requested, and the row
+    // requests read them from LDS.  (Per-lane lookups cost N loads and N registers per lane and tile; and loads retire in order,
+    // so a lookup queued behind the previous tile's rows could not be consumed before those had landed.)  Positions past `nkeys`
+    // repeat the last valid row.  An int64 table contributes its low words (cache rows are < 2^31).
+    SGLK_DEV static void lookup_dma(unsigned* ids, const KvSource& src, int p0, int nkeys, int lane) {
+        const int rr = lane < nkeys ? lane : nkeys - 1;
+        const unsigned char* g = reinterpret_cast<const unsigned char*>(src.page) + (int64_t)(p0 + rr) * (src.page_is64 ? 8 : 4);
+        __builtin_amdgcn_global_load_lds((dma_gptr_t)g, (dma_lptr_t)ids, 4, 0, 0);
+    }
+    template <int AUX>   // 2 = non-temporal: rows that one workgroup reads once need not stay in L2 / the Infinity Cache
+    SGLK_DEV static void issue_rows(unsigned char* lds, const KvSource& src, const unsigned* ids, int wave, int lane) {
+        constexpr int MASK = Swz<CH>::mask;
+        int tok[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) tok[i] = (int)ids[(i * THREADS + wave * 64 + lane) / CH];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int c = i * THREADS + wave * 64 + lane;
+            const int row = c / CH, slot = c - row * CH;
+            const unsigned short* g = src.buf + (int64_t)tok[i] * src.buf_stride_tok + ((slot ^ (row & MASK)) << 3);
+            __builtin_amdgcn_global_load_lds((dma_gptr_t)g, (dma_lptr_t)(lds + (i * THREADS + wave * 64) * 16), 16, 0, AUX);
+        }
+    }
+    SGLK_DEV static void issue(unsigned char* lds, const KvSource& src, int p0, int nkeys, int wave, int lane) {
+        constexpr int MASK = Swz<CH>::mask;
+        constexpr int HALF = (N + 1) / 2;
+        // two passes per half: all row lookups first (independent loads, one wait), then the DMA instructions
+#pragma unroll
+        for (int h0 = 0; h0 < N; h0 += HALF) {
+            const unsigned short* g[HALF];
+#pragma unroll
+            for (int j = 0; j < HALF; ++j) {
+                const int i = h0 + j;
+                if (i < N) {
+                    const int c = i * THREADS + wave * 64 + lane;        // linear chunk of the image this lane fills
+                    const int row = c / CH, slot = c - row * CH;
+                    const int rr = row < nkeys ? row : nkeys - 1;
+                    g[j] = kv_row_paged(src, p0 + rr) + ((slot ^ (row & MASK)) << 3);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < HALF; ++j) {
+                const int i = h0 + j;
+                if (i < N)
+                    __builtin_amdgcn_global_load_lds((dma_gptr_t)g[j], (dma_lptr_t)(lds + (i * THREADS + wave * 64) * 16), 16, 0, 0);
+            }
+        }
     }
 };
 

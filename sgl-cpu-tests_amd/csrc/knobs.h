@@ -36,6 +36,7 @@ struct Knobs {
     int w_nt = -1;               // SGLK_W_NT: 1 / 0 = decode-size MoE kernels read the expert weights non-temporal / not (-1 = from 32 routed rows on)
     int dec_fold = -1;           // SGLK_DEC_FOLD: 0 = decode_attention's cache write always as its own launch (-1 = folded when small)
     int dec_splits = 0;          // SGLK_DEC_SPLITS: KV splits decode_attention uses (0 = one round of workgroups, -1 = all the scratch has)
+    int decm_wide_cols = 32;     // SGLK_DECM_WIDE_COLS: columns per workgroup of decode_attention_multi on wide heads (D >= 256) with more than 32 columns: 32 = two value slices per column tile, or 64 = one (spills; A/B)
     int attn_nw = 0;             // SGLK_ATTN_NW: waves per extend-attention workgroup (4 / 8); 0 = by launch size
     int attn_pair = -1;          // SGLK_ATTN_PAIR: heavy + light causal query blocks in one workgroup (0 / 1); unset = by launch size
     int attn_pp = -1;            // SGLK_ATTN_PP: 0 = one-phase extend kernel for D = DV = 128 too (A/B)

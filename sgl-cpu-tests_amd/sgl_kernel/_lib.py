@@ -147,6 +147,11 @@ class DecodeAttentionFp8kvArgs(ctypes.Structure):
     _fields_ = DecodeAttentionArgs._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float)]
 
 
+class DecodeAttentionMultiArgs(ctypes.Structure):
+    """Mirror of `sglk_decode_attention_multi_args`: the decode args (B = requests) plus the query tokens per request."""
+    _fields_ = DecodeAttentionArgs._fields_ + [("Q", ctypes.c_int32)]
+
+
 class ExtendAttentionFp8kvArgs(ctypes.Structure):
     """Mirror of `sglk_extend_attention_fp8kv_args`: the extend args plus the cache scales and the optional write locations."""
     _fields_ = ExtendAttentionArgs._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float),
@@ -236,6 +241,7 @@ _SIGNATURES = {
     "sglk_flash_attn_varlen": (ctypes.c_int, [ctypes.POINTER(FlashAttnVarlenArgs), ctypes.c_void_p]),
     "sglk_decode_attention": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionArgs), ctypes.c_void_p]),
     "sglk_decode_attention_fp8kv": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionFp8kvArgs), ctypes.c_void_p]),
+    "sglk_decode_attention_multi": (ctypes.c_int, [ctypes.POINTER(DecodeAttentionMultiArgs), ctypes.c_void_p]),
     "sglk_extend_attention_fp8kv": (ctypes.c_int, [ctypes.POINTER(ExtendAttentionFp8kvArgs), ctypes.c_void_p]),
     "sglk_stage_timer_create": (ctypes.c_void_p, [ctypes.c_int32]),
     "sglk_stage_timer_destroy": (None, [ctypes.c_void_p]),

@@ -1118,6 +1118,37 @@ def decode_attention_fp8kv(query, k_buffer, v_buffer, output, key, value, loc, a
     _lib.check(_lib.lib().sglk_decode_attention_fp8kv(ctypes.byref(args), _stream(query)), what)
 
 
+# decode_attention_multi: the project's own operator -- decode_attention_cpu with q_len new tokens per request in one pass over
+# the cache (the verify step of speculative decoding; include/sglk.h, csrc/attention_decode_multi.hip).  Rows b * q_len + t of
+# query / key / value / output / loc belong to request b; b_seq_len counts the new tokens.
+_DEF.define("decode_attention_multi(Tensor query, Tensor(a!) k_buffer, Tensor(b!) v_buffer, Tensor(c!) output, "
+            "Tensor key, Tensor value, Tensor loc, Tensor(d!) attn_logits, Tensor req_to_token, Tensor b_req_idx, "
+            "Tensor b_seq_len, int q_len, float sm_scale, float logit_cap) -> ()")
+
+
+def decode_attention_multi(query, k_buffer, v_buffer, output, key, value, loc, attn_logits, req_to_token, b_req_idx,
+                           b_seq_len, q_len, sm_scale, logit_cap):
+    what = "decode_attention_multi"
+    for t, n in ((query, "query"), (k_buffer, "k_buffer"), (v_buffer, "v_buffer"), (output, "output"), (key, "key"),
+                 (value, "value")):
+        _thd(t, f"{what}: {n}")
+    T = query.shape[0]
+    if q_len < 1 or T % q_len != 0 or T // q_len != b_seq_len.numel() or b_req_idx.numel() != b_seq_len.numel():
+        raise RuntimeError(f"{what}: {T} query rows are not q_len = {q_len} (>= 1) rows for each of the {b_seq_len.numel()} "
+                           "requests of b_seq_len / b_req_idx")
+    if loc.dim() != 1 or loc.numel() != T:
+        raise RuntimeError(f"{what}: loc must have one entry per query row ({T})")
+    if k_buffer.shape[2] != query.shape[2] or v_buffer.shape[1] != k_buffer.shape[1]:
+        raise RuntimeError(f"{what}: k_buffer / v_buffer do not match the query's head dim or each other's heads")
+    if attn_logits.dim() == 4 and not 1 <= attn_logits.shape[2] <= 64:
+        raise RuntimeError(f"{what}: attn_logits must have 1 .. 64 splits, got {attn_logits.shape[2]}")
+    # the shared checks see the T rows as decode's batch; the struct then carries the requests and q_len
+    args, keep = _decode_args(_lib.DecodeAttentionMultiArgs, what, query, k_buffer, v_buffer, output, key, value, loc,
+                              attn_logits, req_to_token, b_req_idx, b_seq_len, sm_scale, logit_cap, Q=int(q_len))
+    args.B = T // q_len
+    _lib.check(_lib.lib().sglk_decode_attention_multi(ctypes.byref(args), _stream(query)), what)
+
+
 # extend_attention_fp8kv: the project's own operator -- extend_attention_cpu over the float8_e4m3fn cache of
 # decode_attention_fp8kv (include/sglk.h, csrc/attention_extend_fp8kv.hip): the paged prefix is read as fp8 * scale, the extend
 # tokens in bf16 as given; with out_cache_loc their quantised rows are written into the cache (the decode operator's rounding).
@@ -1174,3 +1205,4 @@ _impl("extend_attention_cpu", extend_attention_cpu, lambda a, args: a is args[3]
 _impl("extend_attention_fp8kv", extend_attention_fp8kv, lambda a, args: a is args[3] or a is args[4] or a is args[5])
 _impl("decode_attention_cpu", decode_attention_cpu, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])
 _impl("decode_attention_fp8kv", decode_attention_fp8kv, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])
+_impl("decode_attention_multi", decode_attention_multi, lambda a, args: a is args[1] or a is args[2] or a is args[3] or a is args[7])

@@ -2,7 +2,7 @@
 """Secondary measurements (not the driver's bench.py): the M sweep of fp8 fused_experts and the other
 operators of SURVEY.md §8 at the shapes the reference benches, each against the roofline that bounds it.
 
-    python tools/bench_ops.py [moe|moe_literal|moe_int8|gemm|mxfp4|bmm|attn|absorb|rows|all] > bench_ops.json
+    python tools/bench_ops.py [moe|moe_literal|moe_int8|gemm|mxfp4|bmm|attn|decode_multi|absorb|rows|all] > bench_ops.json
 
 Prints one JSON object per line.  HIP-event timing on the current stream, warm-up, rotating clones where the working
 set would otherwise sit in the 256 MiB Infinity Cache.
@@ -443,6 +443,77 @@ def bench_decode_fp8kv():
                  vs_bf16_device=round(dev["bf16"] / dev[k], 3))
 
 
+def bench_decode_multi():
+    """decode_attention_multi at Q = 4 new tokens per request against the two routes there were before it, in the same run:
+    Q calls of decode_attention_cpu (one per draft position, each over its own sequence length) and, where extend attention has
+    the head dims, extend_attention_cpu with extend_len = Q.  Device time per step from hipGraph replays, three alternating runs
+    each (median reported, all kept); the library's A/B knobs of the new path ride along as variants.  bytes = one pass over the
+    cache rows.  max_diff_vs_decode: largest output difference between the new operator and the Q decode calls."""
+    g = torch.Generator(device="cuda").manual_seed(5)
+    dt, Q, B, S = torch.bfloat16, 4, 64, 4096
+    lib = sgl_kernel._lib.lib()
+
+    def with_env(fn, **env):
+        def run():
+            os.environ.update(env)
+            lib.sglk_reload_env()
+            try:
+                return graph_ms(fn)
+            finally:
+                for k in env:
+                    del os.environ[k]
+                lib.sglk_reload_env()
+        return run
+    for (HQ, HKV, D, DV, alias) in ((32, 8, 128, 128, False), (16, 1, 576, 512, True)):
+        total, T, sm = B * S, B * Q, 1.0 / D ** 0.5
+        q = torch.randn(T, HQ, D, device="cuda", generator=g).to(dt)
+        kb = torch.randn(total, HKV, D, device="cuda", generator=g).to(dt)
+        key = torch.randn(T, HKV, D, device="cuda", generator=g).to(dt)
+        vb = kb.narrow(2, 0, DV) if alias else torch.randn(total, HKV, DV, device="cuda", generator=g).to(dt)
+        val = key.narrow(2, 0, DV) if alias else torch.randn(T, HKV, DV, device="cuda", generator=g).to(dt)
+        o, o1 = (torch.zeros(T, HQ, DV, device="cuda", dtype=dt) for _ in range(2))
+        logits = torch.empty(T, HQ, 8, DV + 1, device="cuda", dtype=torch.float32)
+        rtt = torch.arange(total, device="cuda").view(B, S)
+        loc = rtt[:, S - Q:].reshape(-1).contiguous()
+        seq = torch.full((B,), S, device="cuda", dtype=torch.int64)
+        ridx = torch.arange(B, device="cuda")
+        # one decode call per draft position t: rows t, t + Q, ... of the step, sequence length S - Q + t + 1
+        per_t = [dict(q=q[t::Q].contiguous(), key=key[t::Q].contiguous(), val=val[t::Q].contiguous(), loc=loc[t::Q].contiguous(),
+                      o=torch.zeros(B, HQ, DV, device="cuda", dtype=dt), seq=seq - Q + t + 1) for t in range(Q)]
+        if alias:
+            for d in per_t:
+                d["val"] = d["key"].narrow(2, 0, DV)
+
+        def multi():
+            ops.decode_attention_multi(q, kb, vb, o, key, val, loc, logits, rtt, ridx, seq, Q, sm, 0.0)
+
+        def q_decodes():
+            for d in per_t:
+                ops.decode_attention_cpu(d["q"], kb, vb, d["o"], d["key"], d["val"], d["loc"], logits[:B], rtt, ridx, d["seq"], sm, 0.0)
+        calls = {"multi": lambda: graph_ms(multi), "q_decode_calls": lambda: graph_ms(q_decodes)}
+        if alias:    # 64 columns on a wide head: two blocks of 32 (default) against one block of 64
+            calls["multi_wide_cols_64"] = with_env(multi, SGLK_DECM_WIDE_COLS="64")
+        else:        # one column block: non-temporal cache rows (default) against the default cache policy
+            calls["multi_nt_off"] = with_env(multi, SGLK_DEC_NT="0")
+            ext = torch.full((B,), Q, device="cuda", dtype=torch.int32)
+            start = torch.arange(B, device="cuda", dtype=torch.int32) * Q
+            calls["extend_len_q"] = lambda: graph_ms(
+                lambda: ops.extend_attention_cpu(q, key, val, o1, kb, vb, rtt, ridx, seq, ext, start, Q, sm, 0.0))
+        multi(); q_decodes()
+        torch.cuda.synchronize()
+        diff = max((o[t::Q].float() - d["o"].float()).abs().max().item() for t, d in enumerate(per_t))
+        runs = {n: [] for n in calls}
+        for _ in range(3):
+            for n, f in calls.items():
+                runs[n].append(f())
+        dev = {n: sorted(r)[1] for n, r in runs.items()}
+        byts = total * HKV * (D if alias else D + DV) * 2
+        for n in calls:
+            emit(op="decode_multi_" + n, B=B, Q=Q, HQ=HQ, HKV=HKV, D=D, DV=DV, seq=S, v_alias=alias, ms_device=round(dev[n], 4),
+                 ms_device_runs=[round(r, 4) for r in runs[n]], gbps_one_pass=round(byts / dev[n] / 1e6, 1),
+                 vs_multi=round(dev[n] / dev["multi"], 3), max_diff_vs_decode=round(diff, 5))
+
+
 def bench_extend_fp8kv():
     """extend_attention_fp8kv (a) against extend_attention_cpu on a bf16 copy of the same cache made outside the timed region (b),
     and against what a user of the fp8 cache does without it, a torch dequantisation of the prefix rows to bf16 plus (b), both
@@ -542,7 +613,7 @@ def bench_rows():
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
-    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "decode_fp8kv": bench_decode_fp8kv, "extend_fp8kv": bench_extend_fp8kv, "absorb": bench_absorb, "rows": bench_rows}
+    table = {"moe": bench_moe, "moe_literal": bench_moe_literal, "moe_offload": bench_moe_offload, "moe_int8": bench_moe_int8, "gemm": bench_gemm, "shared": bench_shared, "block": bench_block, "mxfp4": bench_mxfp4, "bmm": bench_bmm, "attn": bench_attn, "decode_fp8kv": bench_decode_fp8kv, "decode_multi": bench_decode_multi, "extend_fp8kv": bench_extend_fp8kv, "absorb": bench_absorb, "rows": bench_rows}
     for name, fn in table.items():
         if which in ("all", name):
             fn()
